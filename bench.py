@@ -13,11 +13,14 @@ N > 1 (torch.distributed.run, one process per GPU): independent env blocks per r
 rank), no data-path collective ("scaling": "weak"); `--shared-policy` adds the RCCL all-reduce of
 flat actor/critic gradients (BASELINE config 5). Rank 0 prints one JSON line.
 
-Besides `value`, the line carries `roofline` for the dominant kernel (HIP-event timed inside the
-timed region on the launch stream), the step kernel's HBM figure on a large-N sweep
-(`step_kernel`, the 2^24-env point), the per-tick time at 65 536 envs in both launch forms
-(`tick_forms`: nav_act + nav_agent_step_indexed vs the fused nav_act_tick), and
-`cpu_baseline` (the oracle CPU port of the same loop, rank 0 only, bounded sample).
+A plain run sets up, warms up, times `--steps` steps (no HIP events inside the timed region),
+writes the last timed step's results when `--dump-outputs DIR` is given, and prints the line with
+`value` and `ms_per_step`. Everything else is behind `--full`: the per-kernel breakdown pass,
+`roofline` for the dominant kernel (HIP-event timed inside the timed region on the launch
+stream), the longer event-free run (`timed_long`), the step kernel's HBM figure on a large-N
+sweep (`step_kernel`, the 2^24-env point), the per-tick time at 65 536 envs in both launch forms
+(`tick_forms`: nav_act + nav_agent_step_indexed vs the fused nav_act_tick), the update-to-data
+sweep, and `cpu_baseline` (the oracle CPU port of the same loop, rank 0 only, bounded sample).
 """
 import argparse
 import json
@@ -150,6 +153,14 @@ def parse():
     ap.add_argument("--shared-policy", action="store_true")
     # shared policy: the next collect on a second stream beside the last epoch's all-reduce
     ap.add_argument("--overlap-collect", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel breakdown, the roofline of the dominant kernel "
+                         "(HIP events inside the timed region), timed_long, tick_forms, the "
+                         "step-kernel sweep, the update-to-data sweep and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as "
+                         "DIR/<name>.npy (float32 / float64)")
+    # the --no-* switches and --long-steps trim a --full run; a plain run has none of these legs
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--no-utd-sweep", action="store_true")
@@ -405,6 +416,48 @@ def utd_sweep(args, dev, points=((8192, 2), (32768, 2), (32768, 8)), steps=30):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def step_outputs(tr):
+    """What one VecTrainer.step() leaves for its caller, by name: the actions the actor chose, the
+    tick's results (next_state, goal_term, flags), the per-env state after the auto-reset, the
+    replay rows this step pushed (in env order) and the parameters of the six networks after the
+    learner's epochs."""
+    env, rep = tr.env, tr.replay
+    out = {"action": tr.action, "next_state": env.next_state, "goal_term": env.goal_term,
+           "flags": env.flags}
+    for k in tr.ENV_STATE:
+        out["env_" + k] = getattr(env, k)
+    slots = (rep.position - tr.n + torch.arange(tr.n, device=rep.rows.device)) % rep.capacity
+    out["replay_rows"] = rep.rows[slots]
+    for k, net in tr.td3.networks().items():
+        out["net_" + k] = net.params
+    return out
+
+
+def dump_outputs(tr, path):
+    """--dump-outputs: step_outputs() as DIR/<name>.npy, float32 tensors as they are and every
+    other dtype as float64 (exact for the integer state). Whole arrays while they fit 64 MB in all
+    (16.9 MB at the default sizes); past that, an array over its equal share of the budget is
+    written as a fixed seeded sample of its flattened entries."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {}
+    for k, t in step_outputs(tr).items():
+        a = t.detach().cpu().numpy()
+        arrays[k] = a if a.dtype == np.float32 else a.astype(np.float64)
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    fits = sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES
+    for i, (k, a) in enumerate(sorted(arrays.items())):
+        if not fits and a.nbytes > share:
+            keep = share // a.itemsize
+            ix = np.sort(np.random.default_rng(i).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[ix]
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ:
@@ -449,21 +502,24 @@ def main():
     for _ in range(max(args.warmup, 1)):
         tr.step()
     torch.cuda.synchronize()
-    bd = prof.KernelTimer()
-    with prof.timing(bd):
-        for _ in range(2):
-            tr.step()
-    breakdown = bd.summary()
-    # the dominant KERNEL (the all-reduce region is a collective, reported apart)
-    dominant = max((k for k in breakdown if k != "allreduce"),
-                   key=lambda k: breakdown[k]["total_ms"])
+    tracked = []
+    if args.full:
+        bd = prof.KernelTimer()
+        with prof.timing(bd):
+            for _ in range(2):
+                tr.step()
+        breakdown = bd.summary()
+        # the dominant KERNEL (the all-reduce region is a collective, reported apart)
+        dominant = max((k for k in breakdown if k != "allreduce"),
+                       key=lambda k: breakdown[k]["total_ms"])
+        tracked = [dominant] + (["allreduce"] if hook is not None else [])
 
     # ---- timed region
-    # the dominant kernel's launches are bracketed by HIP event pairs on its launch stream, one
-    # launch in EVENT_SAMPLE (each record stalls the stream a few us; bracketing every launch
-    # cost 2.6 % of the step, profiles/r03c_bench.json value vs timed_long); with a shared
-    # policy the all-reduce messages are sampled the same way
-    tracked = [dominant] + (["allreduce"] if hook is not None else [])
+    # --full: the dominant kernel's launches are bracketed by HIP event pairs on its launch
+    # stream, one launch in EVENT_SAMPLE (each record stalls the stream a few us; bracketing
+    # every launch cost 2.6 % of the step, profiles/r03c_bench.json value vs timed_long); with a
+    # shared policy the all-reduce messages are sampled the same way. A plain run (and
+    # --no-timed-events) records no event: the timer tracks no region
     timer = prof.KernelTimer([] if args.no_timed_events else tracked,
                              sample_every=EVENT_SAMPLE)
     barrier(ws)
@@ -482,9 +538,32 @@ def main():
     ksum = timer.summary()
     env_steps = args.envs * args.steps * ws
     value = env_steps / dt
+    if args.dump_outputs:  # the last timed step's results, before any further step runs
+        dump_outputs(tr, args.dump_outputs if rank == 0 else
+                     os.path.join(args.dump_outputs, "rank%d" % rank))
+    head = {
+        "metric": "env-steps/sec at 65 536 parallel envs (full residual-TD3 update)",
+        "value": value, "unit": "env-steps/s", "n_gpus": ws, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": DTYPE,
+        "accuracy": ACCURACY,
+        "data": "synthetic (Philox start/goal pairs, generated fields, batched-CEM demo sets)",
+        "config": {"workload": "config3: 65536 envs + residual-TD3 (2x256 MLPs)",
+                   "envs_per_gpu": args.envs, "envs_per_group": args.envs_per_group,
+                   "hidden": args.hidden, "layers": args.layers, "batch": args.batch,
+                   "td3_epochs_per_step": args.updates,
+                   "rank_batch": rank_batch,
+                   "update_to_data": args.updates * args.batch / args.envs,
+                   "parallelism": ("dp%d-shared-policy%s" % (
+                                       ws, "-overlap-collect" if tr.overlap_collect else "")
+                                   if args.shared_policy and ws > 1
+                                   else "independent-env-blocks x%d" % ws)},
+        "full": args.full,
+    }
     # a longer event-free timed run beside the contract's K steps (extra key)
     timed_long = None
-    if args.long_steps > 0:
+    if args.full and args.long_steps > 0:
         dtl = timed_steps(tr, args.long_steps, ws, dev)
         timed_long = {"steps": args.long_steps, "ms_per_step": 1e3 * dtl / args.long_steps,
                       "value": args.envs * args.long_steps * ws / dtl,
@@ -493,6 +572,8 @@ def main():
     if rank == 0 and args.no_timed_events:
         print(json.dumps({"value": value, "ms_per_step": 1e3 * dt / args.steps,
                           "no_timed_events": True}), flush=True)
+    elif rank == 0 and not args.full:
+        print(json.dumps(head), flush=True)
     elif rank == 0:
         d = ksum[dominant]
         traffic, traffic_src = pmc_traffic(dominant)
@@ -573,35 +654,19 @@ def main():
         # CPU baseline: rank 0 at N = 1 only (a reported baseline, not part of the scaling runs)
         cpu = None if (args.no_cpu_baseline or ws > 1) else cpu_baseline(args, tr)
         utd = None if (args.no_utd_sweep or ws > 1) else utd_sweep(args, dev)
-        line = {
-            "metric": "env-steps/sec at 65 536 parallel envs (full residual-TD3 update)",
-            "value": value, "unit": "env-steps/s", "n_gpus": ws, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": DTYPE,
-            "accuracy": ACCURACY,
-            "data": "synthetic (Philox start/goal pairs, generated fields, batched-CEM demo sets)",
-            "config": {"workload": "config3: 65536 envs + residual-TD3 (2x256 MLPs)",
-                       "envs_per_gpu": args.envs, "envs_per_group": args.envs_per_group,
-                       "hidden": args.hidden, "layers": args.layers, "batch": args.batch,
-                       "td3_epochs_per_step": args.updates,
-                       "rank_batch": rank_batch,
-                       "update_to_data": args.updates * args.batch / args.envs,
-                       "parallelism": ("dp%d-shared-policy%s" % (
-                                           ws, "-overlap-collect" if tr.overlap_collect else "")
-                                       if args.shared_policy and ws > 1
-                                       else "independent-env-blocks x%d" % ws)},
-            "roofline": roof,
-            "step_kernel": step_k,
-            "tick_forms": forms,
-            "step_kernel_sweep": sweep,
-            "kernels": {k: {"avg_us": round(v["avg_us"], 2), "launches_per_step":
-                            v["launches"] / 2, "ms_per_step": v["total_ms"] / 2}
-                        for k, v in breakdown.items()},
-            "cpu_baseline": cpu,
-            "timed_long": timed_long,
-            "utd_sweep": utd,
-        }
+        line = dict(
+            head,
+            roofline=roof,
+            step_kernel=step_k,
+            tick_forms=forms,
+            step_kernel_sweep=sweep,
+            kernels={k: {"avg_us": round(v["avg_us"], 2), "launches_per_step":
+                         v["launches"] / 2, "ms_per_step": v["total_ms"] / 2}
+                     for k, v in breakdown.items()},
+            cpu_baseline=cpu,
+            timed_long=timed_long,
+            utd_sweep=utd,
+        )
         if hook is not None:
             ar = ksum.get("allreduce")
             line["allreduce"] = {

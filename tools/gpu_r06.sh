@@ -33,8 +33,8 @@ ROOT=$(pwd)
 O=$ROOT/gpurun_out/$TAG
 mkdir -p "$O"
 : > "$O/status.txt"
-SHORT="--steps 20 --warmup 3 --no-cpu-baseline --no-utd-sweep --no-sweep --long-steps 0"
-PMCB="--steps 4 --warmup 2 --no-cpu-baseline --no-utd-sweep --no-sweep --long-steps 0"
+SHORT="--full --steps 20 --warmup 3 --no-cpu-baseline --no-utd-sweep --no-sweep --long-steps 0"
+PMCB="--full --steps 4 --warmup 2 --no-cpu-baseline --no-utd-sweep --no-sweep --long-steps 0"
 run() {
   local name=$1 t=$2; shift 2
   local t0=$(date +%s)
@@ -63,7 +63,7 @@ for step in "$@"; do
           run ab_new_$r 200 python bench.py $SHORT --steps 100 --warmup 10 --no-timed-events
           (cd abl/prev && run ab_old_$r 200 python bench.py $SHORT --steps 100 --warmup 10 --no-timed-events)
         done ;;
-    bench) run bench 500 python bench.py ;;
+    bench) run bench 500 python bench.py --full ;;
     prof) run prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -o run -- python bench.py $SHORT ;;
     pmc) run pmc_fetch 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/fetch" -o run -- python bench.py $PMCB &&
          run pmc_write 150 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/write" -o run -- python bench.py $PMCB &&
@@ -99,9 +99,9 @@ for step in "$@"; do
     clock) run clock 200 python tools/withlib.py "$ROOT/abl/libnavenv_clock.so" tools/clock_probe.py --seconds 3 ;;
     sphost) run sphost 300 python tools/shared_policy_host.py ;;
     launch) export NAV_DIST_REHEARSAL=1
-            run launch_blocks 300 python bench.py --gpus 2 --steps 20 --warmup 2 --long-steps 0 &&
-            run launch_shared 300 python bench.py --gpus 2 --steps 20 --warmup 2 --long-steps 0 --shared-policy &&
-            run launch_overlap 300 python bench.py --gpus 2 --steps 20 --warmup 2 --long-steps 0 --shared-policy --overlap-collect
+            run launch_blocks 300 python bench.py --full --gpus 2 --steps 20 --warmup 2 --long-steps 0 &&
+            run launch_shared 300 python bench.py --full --gpus 2 --steps 20 --warmup 2 --long-steps 0 --shared-policy &&
+            run launch_overlap 300 python bench.py --full --gpus 2 --steps 20 --warmup 2 --long-steps 0 --shared-policy --overlap-collect
             unset NAV_DIST_REHEARSAL ;;
     dbgvar) for v in $DVARS; do run dbg_$v 120 python tools/withlib.py "$ROOT/abl/libnavenv_$v.so" tools/dbg_bits.py --batch 16421; done ;;
     dbgbits) run dbgbits_16421 120 python tools/dbg_bits.py --batch 16421 &&
