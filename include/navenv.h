@@ -39,6 +39,7 @@ extern "C" {
 #define NAV_TAG_NOISE 3  /* ctr = (0, env, 3, step)           exploration noise pair    */
 #define NAV_TAG_SAMPLE 4 /* ctr = (i, 0, 4, update)           replay sample index       */
 #define NAV_TAG_TNOISE 5 /* ctr = (row, 0, 5, update)         target-smoothing noise    */
+#define NAV_TAG_TEST 6   /* ctr = (0, env, 6, episode)        test-episode start draw   */
 
 /* Constants of constants.py / robot.py as a POD (defaults in nav_default_params). */
 typedef struct nav_params {
@@ -309,6 +310,29 @@ int nav_act_tick(const nav_params* p, const nav_mlp* actor, const nav_env_soa* e
                  const double* demo_xy, const int64_t* demo_off, int32_t envs_per_group,
                  const int64_t* cell_start, const int32_t* cand, double* action_out,
                  double* reward_out, void* stream);
+
+/* Per-env results of nav_test_rollout (device). */
+typedef struct nav_test_out {
+    uint8_t* reached;       /* [n] 1 = a step ended within goal_threshold of the goal          */
+    int32_t* steps;         /* [n] the 1-based step that reached, else max_steps               */
+    double*  best_distance; /* [n] min over the steps taken of ||s - goal|| (the reaching step
+                               included; robot-learning.py:113-114)                            */
+    double*  final_state;   /* [n][2] state after the last step taken                          */
+    double*  traj;          /* nullable [max_steps][n][2]: state after each step; a stopped
+                               env's later rows repeat its final state                         */
+} nav_test_out;
+
+/* A whole test episode of every env in ONE launch (robot-learning.py:78, 104-117): from its start
+ * (`start` [n][2] if given, else region_sample(region[e], u01(w.x, w.y), u01(w.z, w.w)) with w =
+ * philox(0, e, NAV_TAG_TEST, episode): Environment.reset's formula on a stream of its own), env e
+ * repeats nav_act mode 1 (no noise) and nav_env_step until a step ends within goal_threshold of
+ * its goal or max_steps (1 .. 1 << 20) steps are taken. Same states as that two-launch loop, bit
+ * for bit. Reads env->goal (and env->region when start is NULL), the field and the actor; writes
+ * only `out`: the env SoA, the replay ring and the actor are untouched. */
+int nav_test_rollout(const nav_params* p, const nav_mlp* actor, const nav_env_soa* env,
+                     const float* field, const double* start, uint32_t episode,
+                     int32_t max_steps, const nav_test_out* out, void* stream);
+
 /* Generic forward of up to 2 networks sharing one input (twin critics), rows [M]:
  * x = in[m*ld_in + in_col + 0..d_in) (f32). out_mode 0: out[m*ld_out + out_col + j] = y;
  * out_mode 1 (target policy smoothing, robot.py:336-339): out = clamp(y + clamp(policy_noise*eps,

@@ -1239,6 +1239,120 @@ __global__ __launch_bounds__(kBlock, 1) void k_mlp_fwd(FwdArgs a) {
     }
 }
 
+// ---------------- greedy test episodes (robot-learning.py:78, 104-117) ----------------
+struct TestArgs {
+    MlpDev net;              // the actor (2 -> 2)
+    int64_t n;
+    const double2* goal;     // env->goal
+    const double4* region;   // env->region (read only when start is null)
+    const double2* start;    // nullable [n]
+    const float2* field;
+    double max_action, goal_threshold;
+    uint32_t seed_lo, seed_hi, episode;
+    int32_t max_steps;
+    nav_test_out out;
+};
+
+// bytes of the row kernels' LDS layout (lds_bytes) on the device side: the test rollout parks its
+// two loop flags right behind it
+__host__ __device__ constexpr size_t lds_bytes_c(int hp, int tm) {
+    return lds_floats(hp, tm) * 4 + stage_bytes(tm, hp);
+}
+
+// One workgroup = TM envs for a whole test episode: thread t < TM keeps env row0 + t's state,
+// goal, best distance, step count and reached flag in registers and, per step, writes the
+// baseline input row, takes its residual from the block's forward (fwd_net, as k_mlp_fwd), forms
+// the testing-mode action (OUT_ACT's expressions, no noise) and moves (k_env_step's). A row that
+// has reached its goal keeps its state: its input row then repeats, it still takes part in the
+// GEMMs and barriers, and its results are dropped. The block leaves the loop when no row runs;
+// the two LDS flags alternate by step parity, so a step costs one barrier on top of fwd_net's
+// (step t's runners raise flag t & 1 while thread 0 clears the other, which was last read a
+// step ago and is next raised a step ahead, both behind fwd_net's barriers).
+template <int NT, int RT>
+__global__ __launch_bounds__(kBlock, 1) void k_test_rollout(TestArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int hp = NT * 32, SS = hp + 4, TM = RT * 32;
+    const int tid = threadIdx.x;
+    const MlpDev& net = a.net;
+    const int64_t n = a.n, row0 = (int64_t)blockIdx.x * TM, r = row0 + tid;
+    float* act = smem;
+    float* xin = smem + TM * SS;   // [TM][4]
+    float* red = xin + TM * 4;     // [2][PARTS][TM]
+    _Float16* stage = reinterpret_cast<_Float16*>(smem + lds_floats(hp, TM));
+    int* flag = reinterpret_cast<int*>(reinterpret_cast<char*>(smem) + lds_bytes_c(hp, TM));
+    // layer 0's per-lane weights and bias: once, outside the step loop
+    const L0Pre l0 = load_l0<NT>(net);
+    const bool mine = tid < TM && r < n;
+    double2 s = make_double2(0.0, 0.0), g = s;
+    if (mine) {
+        g = a.goal[r];
+        if (a.start) {
+            s = a.start[r];
+        } else {
+            // Environment.reset's formula (environment.py:130-137) on the test stream
+            const uint4 w = philox(0u, (uint32_t)r, NAV_TAG_TEST, a.episode, a.seed_lo, a.seed_hi);
+            const double4 rg = a.region[r];
+            const double reg[4] = {rg.x, rg.y, rg.z, rg.w};
+            s = region_sample(reg, u01(w.x, w.y), u01(w.z, w.w));
+        }
+    }
+    double best = __builtin_huge_val();
+    int32_t steps = a.max_steps;
+    uint8_t reached = 0;
+    bool run = mine;
+    double2* traj = reinterpret_cast<double2*>(a.out.traj);
+    if (tid == 0) flag[0] = flag[1] = 0;
+    __syncthreads();
+    int t = 1;
+    for (; t <= a.max_steps; ++t) {
+        // robot.py:586-588 baseline = state - goal, then torch.FloatTensor (f64 -> f32)
+        if (tid < TM)
+            *reinterpret_cast<float4*>(xin + tid * 4) =
+                mine ? make_float4((float)(s.x - g.x), (float)(s.y - g.y), 0.f, 0.f)
+                     : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (run) flag[t & 1] = 1;
+        if (tid == 0) flag[(t + 1) & 1] = 0;
+        // the row's field value does not depend on its action: in flight under the network pass
+        float2 fv = make_float2(0.f, 0.f);
+        if (run) fv = field_at(a.field, s);
+        __syncthreads();
+        if (!__builtin_amdgcn_readfirstlane(flag[t & 1])) break;  // block-uniform
+        f32x16 top[RT][2];
+        fwd_net<NT, RT, kPfWide, 2>(net, act, stage, xin, red, nullptr, 0, nullptr, 0u, row0, n, 0,
+                                    top, -64, &l0);
+        if (run) {
+            // robot.py:589-593, mode 1 (both components by the row's thread, as OUT_TICK)
+            double v[2];
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) {
+                const float y = out_y<RT>(net, red, tid, jj);
+                const double sj = jj == 0 ? s.x : s.y, gj = jj == 0 ? g.x : g.y;
+                v[jj] = clipd((sj - gj) + (double)y, -a.max_action, a.max_action);
+            }
+            // environment.py:122-127
+            const double2 nx = dynamics_f(fv, s, make_double2(v[0], v[1]));
+            if (in_world(nx)) s = nx;
+            // robot-learning.py:107, 113-114
+            const double d = norm2(s.x - g.x, s.y - g.y);
+            best = d < best ? d : best;
+            if (d <= a.goal_threshold) {
+                reached = 1;
+                steps = t;
+                run = false;
+            }
+        }
+        if (traj && mine) traj[(int64_t)(t - 1) * n + r] = s;
+    }
+    if (!mine) return;
+    // steps the block did not take: the final state repeats
+    if (traj)
+        for (int64_t k = t - 1; k < a.max_steps; ++k) traj[k * n + r] = s;
+    a.out.reached[r] = reached;
+    a.out.steps[r] = steps;
+    a.out.best_distance[r] = best;
+    reinterpret_cast<double2*>(a.out.final_state)[r] = s;
+}
+
 // ---------------- row-local backward ----------------
 struct BwdArgs {
     MlpDev net[2];           // 1 or 2 networks (blockIdx.y), same shapes, same input rows
@@ -1959,7 +2073,7 @@ int row_tiles_for(int64_t M, bool tick) { return (!tick && M <= kSmallRows) ? 1 
 // their own objects (this file built with NAV_MLP_PART = NT, see the Makefile) so the heavy
 // template instantiations compile in parallel; the main object (NAV_MLP_PART = 0) dispatches to
 // them through nav_mlp_rows_<NT>(). Argument structs travel as const void* (same definitions).
-enum { FAM_FWD = 0, FAM_BWD = 1, FAM_CRITIC = 2, FAM_ACTOR = 3 };
+enum { FAM_FWD = 0, FAM_BWD = 1, FAM_CRITIC = 2, FAM_ACTOR = 3, FAM_TEST = 4 };
 
 }  // namespace
 
@@ -2040,6 +2154,16 @@ void launch_actor_rows_k(const ActorRowsArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k, dim3(gx, 1u + wy), dim3(kBlock), lds, st, w);
 }
 
+template <int NT, int RT>
+void launch_test_k(const TestArgs& a, hipStream_t st) {
+    constexpr int TM = RT * 32;
+    const size_t lds = lds_bytes_c(NT * 32, TM) + 2 * sizeof(int);  // + the two loop flags
+    auto k = k_test_rollout<NT, RT>;
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+    hipLaunchKernelGGL(k, dim3((unsigned)((a.n + TM - 1) / TM)), dim3(kBlock), lds, st, a);
+}
+
 template <int RT>
 int rows_rt(int fam, int in_mode, int out_mode, const void* args, int n_nets, hipStream_t st) {
     constexpr int NT = NAV_MLP_PART;
@@ -2070,6 +2194,7 @@ int rows_rt(int fam, int in_mode, int out_mode, const void* args, int n_nets, hi
         case FAM_ACTOR:
             launch_actor_rows_k<NT, RT>(*static_cast<const ActorRowsArgs*>(args), st);
             return 0;
+        case FAM_TEST: launch_test_k<NT, RT>(*static_cast<const TestArgs*>(args), st); return 0;
         default: return NAV_EINVAL;
     }
 }
@@ -2231,6 +2356,33 @@ int nav_act_tick(const nav_params* p, const nav_mlp* actor, const nav_env_soa* e
                          envs_per_group > 0 ? envs_per_group : 1, cell_start, cand};
     a.reward_out = reward_out;
     return launch_fwd<IN_BASELINE, OUT_TICK>(a, 1, S(stream));
+}
+
+int nav_test_rollout(const nav_params* p, const nav_mlp* actor, const nav_env_soa* env,
+                     const float* field, const double* start, uint32_t episode,
+                     int32_t max_steps, const nav_test_out* out, void* stream) {
+    TestArgs a{};
+    if (!p || !env || !field || !out || !make_dev(actor, &a.net) || actor->d_in != 2 ||
+        actor->d_out != 2 || max_steps < 1 || max_steps > (1 << 20) || env->n < 0 ||
+        env->n >= ((int64_t)1 << 31))
+        return NAV_EINVAL;
+    if (env->n == 0) return 0;
+    if (!env->goal || (!start && !env->region) || !out->reached || !out->steps ||
+        !out->best_distance || !out->final_state)
+        return NAV_EINVAL;
+    a.n = env->n;
+    a.goal = reinterpret_cast<const double2*>(env->goal);
+    a.region = reinterpret_cast<const double4*>(env->region);
+    a.start = reinterpret_cast<const double2*>(start);
+    a.field = reinterpret_cast<const float2*>(field);
+    a.max_action = p->max_action;
+    a.goal_threshold = p->goal_threshold;
+    a.seed_lo = p->seed_lo;
+    a.seed_hi = p->seed_hi;
+    a.episode = episode;
+    a.max_steps = max_steps;
+    a.out = *out;
+    return rows_dispatch(a.net.hp, FAM_TEST, 0, 0, &a, 1, a.n, S(stream));
 }
 
 int nav_mlp_forward(const nav_mlp* nets, int32_t n_nets, int64_t M, const float* in,

@@ -53,6 +53,11 @@ class NavMlp(C.Structure):
     ]
 
 
+class NavTestOut(C.Structure):
+    _fields_ = [("reached", _vp), ("steps", _vp), ("best_distance", _vp), ("final_state", _vp),
+                ("traj", _vp)]
+
+
 # (name, restype, argtypes) for every entry point of include/navenv.h
 _P = C.POINTER
 SIGNATURES = [
@@ -104,6 +109,8 @@ SIGNATURES = [
     ("nav_act_tick", C.c_int, [_P(NavParams), _P(NavMlp), _P(NavEnvSoa), _vp, _vp, C.c_uint32,
                                C.c_int32, _P(NavReplay), C.c_int64, _P(NavStepOut), _vp, _vp,
                                C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    ("nav_test_rollout", C.c_int, [_P(NavParams), _P(NavMlp), _P(NavEnvSoa), _vp, _vp,
+                                   C.c_uint32, C.c_int32, _P(NavTestOut), _vp]),
     ("nav_mlp_forward", C.c_int, [_P(NavMlp), C.c_int32, C.c_int64, _vp, C.c_int32, C.c_int32,
                                   _P(_vp), C.c_int32, C.c_int32, C.c_int32, _vp, C.c_float,
                                   C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32,

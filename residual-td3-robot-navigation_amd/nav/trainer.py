@@ -124,6 +124,25 @@ class VecTrainer:
         host-side changes to the env state, the replay ring or the actor between steps)."""
         self._collect_ready = None
 
+    # robot-learning.py's testing mode (78, 104-117) over all envs with the online actor
+    def evaluate(self, max_steps=K.TEST_TIMEOUT * K.UPDATE_RATE, episode=0, start=None):
+        """One greedy test episode per env (VecEnv.test_rollout) and its summary as a plain dict.
+        Reads the online actor, the goals and the init regions only: the env state, the replay
+        ring, the step counter and the learner are untouched."""
+        out = self.env.test_rollout(self.td3.actor_network, max_steps, episode=episode,
+                                    start=start)
+        reached = out["reached"].bool()
+        n_reached = int(reached.sum().item())
+        mean_steps = (out["steps"][reached].double().mean().item() if n_reached
+                      else float("nan"))
+        return {"n": self.n,
+                "success_rate": out["reached"].float().mean().item(),
+                "mean_steps_reached": mean_steps,
+                "mean_best_distance": out["best_distance"].mean().item(),
+                "max_best_distance": out["best_distance"].max().item(),
+                "max_steps": int(max_steps),
+                "episode": int(episode)}
+
     def env_steps(self):
         return self.steps * self.n
 

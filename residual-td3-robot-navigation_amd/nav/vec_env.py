@@ -9,8 +9,8 @@ import torch
 
 from . import config as K
 from . import prof
-from ._lib import (NavEnvSoa, NavReplay, NavStepOut, lib, params_struct, ptr, require_gpu,
-                   stream_handle)
+from ._lib import (NavEnvSoa, NavReplay, NavStepOut, NavTestOut, lib, params_struct, ptr,
+                   require_gpu, stream_handle)
 
 
 def make_field(speed, angle, device="cuda"):
@@ -132,6 +132,7 @@ class VecEnv:
         # demo reward fused into the tick launch (nav_agent_step_indexed); False keeps the two
         # launches (A/B and the fused-vs-unfused parity test)
         self.fuse_demo = bool(fuse_demo)
+        self._test_out = {}  # (max_steps, traj) -> test_rollout's output tensors
         if init:
             self.init(demo_flag)
 
@@ -242,6 +243,38 @@ class VecEnv:
                 ptr(action_out), ptr(reward_out), stream_handle(stream))
         replay.advance(self.n)
         return base
+
+    # robot-learning.py:78, 104-117 for every env: one greedy test episode per env in ONE launch
+    # (nav_test_rollout). Reads the goals (and the regions when the starts are drawn), never the
+    # training state: the env SoA, the replay ring and the actor are left as they are.
+    def test_rollout(self, actor, max_steps, episode=0, start=None, traj=False, stream=None):
+        """Per-env device tensors of one test episode: reached [n] u8, steps [n] i32,
+        best_distance [n] f64, final_state [n][2] f64 and (traj=True) traj [max_steps][n][2] f64.
+        `start` [n][2] f64 gives the start states; None draws them from each env's init region on
+        the test stream (NAV_TAG_TEST, `episode`). The tensors are allocated once per
+        (max_steps, traj) and overwritten by the next call with the same pair."""
+        max_steps, key = int(max_steps), (int(max_steps), bool(traj))
+        out = self._test_out.get(key)
+        if out is None:
+            d, n, f64 = self.device, self.n, torch.float64
+            out = {"reached": torch.zeros(n, dtype=torch.uint8, device=d),
+                   "steps": torch.zeros(n, dtype=torch.int32, device=d),
+                   "best_distance": torch.zeros(n, dtype=f64, device=d),
+                   "final_state": torch.zeros(n, 2, dtype=f64, device=d)}
+            if traj:
+                out["traj"] = torch.zeros(max_steps, n, 2, dtype=f64, device=d)
+            self._test_out[key] = out
+        if start is not None:
+            assert start.shape == (self.n, 2) and start.dtype == torch.float64
+        a = actor.desc()
+        o = NavTestOut(*[ptr(out.get(k)) for k in ("reached", "steps", "best_distance",
+                                                   "final_state", "traj")])
+        flops = max_steps * prof.mlp_fwd_flops(2, 2, actor.hidden, actor.n_hidden, self.n)
+        with prof.region("test_rollout", flops):
+            lib().nav_test_rollout(C.byref(self.p), C.byref(a), C.byref(self.soa),
+                                   ptr(self.field), ptr(start), int(episode) & 0xFFFFFFFF,
+                                   max_steps, C.byref(o), stream_handle(stream))
+        return out
 
     def stats(self):
         """Sum of the per-block rows: reward (the final pushed reward, demo term included, in

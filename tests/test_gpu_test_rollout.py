@@ -1,0 +1,325 @@
+"""nav_test_rollout / VecEnv.test_rollout / VecTrainer.evaluate: whole greedy test episodes
+(robot-learning.py:78, 104-117) of every env in one launch, against the two-launch composition it
+fuses (bit for bit), against its own trajectory, against the CPU oracle step by step and over
+whole episodes, its start draw, and its promise to leave the trainer untouched."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+T_BITS = 12  # steps of the bitwise cases
+
+
+@pytest.fixture(scope="module")
+def nav():
+    from nav import _lib
+    _lib.require_gpu()
+    _lib.lib()
+    import nav as navpkg
+    return navpkg
+
+
+def norm2_rows(orc, d):
+    """orc.norm2 (sqrt(fma(y, y, x * x)), the device's norm2) of every row of d [k][2]."""
+    return np.array([orc.norm2(x, y) for x, y in d.tolist()], np.float64).reshape(len(d))
+
+
+def random_field(seed):
+    rng = np.random.default_rng(seed)
+    speed = rng.uniform(0.05, 0.95, (100, 100)).astype(np.float32)  # in (0, 1)
+    angle = rng.uniform(0.0, 1.0, (100, 100)).astype(np.float32)    # in [0, 1]
+    return speed, angle
+
+
+def make_actor(hidden, nh, seed):
+    from nav.mlp import DeviceMLP
+    from oracle.td3_oracle import make_mlp_params
+    p = make_mlp_params(seed, [2] + [hidden] * nh + [2])
+    return DeviceMLP(2, 2, hidden, nh, DEV).load(p), [(torch.tensor(W), torch.tensor(b))
+                                                      for W, b in p]
+
+
+def make_env(n, speed, angle, **overrides):
+    from nav.vec_env import VecEnv, make_field
+    return VecEnv(n, make_field(speed, angle, DEV), seed=77, demo_flag=False, device=DEV,
+                  **overrides)
+
+
+def random_starts(env, seed):
+    """Uniform starts in the world; every 5th env one unit from its goal, so that some rows stop
+    at the first step while their tile goes on."""
+    g = torch.Generator().manual_seed(seed)
+    st = torch.rand(env.n, 2, generator=g, dtype=torch.float64) * 98.0
+    near = torch.arange(env.n) % 5 == 0
+    st[near] = env.goal.cpu()[near] + torch.tensor([0.6, -0.8], dtype=torch.float64)
+    return st.clamp_(0.0, 98.0).to(DEV)
+
+
+def clone_out(out):
+    return {k: v.clone() for k, v in out.items()}
+
+
+def unfused_episode(orc, env, actor, start, T):
+    """The composition the kernel fuses: per step nav_act(mode=1) then nav_env_step on a scratch
+    VecEnv, stopped rows masked back, the stop test on the CPU with the oracle's norm2."""
+    from nav._lib import lib, ptr, stream_handle
+    from nav.vec_env import VecEnv
+    n = env.n
+    sc = VecEnv(n, env.field, device=DEV, init=False)
+    sc.goal.copy_(env.goal)
+    sc.state.copy_(start)
+    thr = env.p.goal_threshold
+    goal = env.goal.cpu().numpy()
+    action = torch.zeros(n, 2, dtype=torch.float64, device=DEV)
+    d = actor.desc()
+    run = np.ones(n, bool)
+    reached = np.zeros(n, np.uint8)
+    steps = np.full(n, T, np.int32)
+    best = np.full(n, np.inf)
+    traj = torch.zeros(T, n, 2, dtype=torch.float64, device=DEV)
+    for t in range(1, T + 1):
+        prev = sc.state.clone()
+        lib().nav_act(C.byref(sc.p), C.byref(d), n, ptr(sc.state), ptr(sc.goal), None, None, 0, 1,
+                      ptr(action), None, stream_handle())
+        sc.step(action)
+        keep = torch.from_numpy(~run).to(DEV)
+        sc.state.copy_(torch.where(keep[:, None], prev, sc.state))
+        traj[t - 1] = sc.state
+        s = sc.state.cpu().numpy()
+        idx = np.nonzero(run)[0]
+        dist = norm2_rows(orc, s[idx] - goal[idx])
+        best[idx] = np.minimum(best[idx], dist)
+        hit = idx[dist <= thr]
+        reached[hit] = 1
+        steps[hit] = t
+        run[hit] = False
+    return {"traj": traj, "final_state": sc.state.clone(), "reached": torch.from_numpy(reached),
+            "steps": torch.from_numpy(steps), "best_distance": torch.from_numpy(best)}
+
+
+_cases = {}
+
+
+def bit_case(orc, hidden, nh, n):
+    """(env, actor, start, the kernel's outputs, the unfused loop's): computed once per shape."""
+    key = (hidden, nh, n)
+    if key not in _cases:
+        speed, angle = random_field(5)
+        env = make_env(n, speed, angle)
+        actor, layers = make_actor(hidden, nh, 31)
+        start = random_starts(env, 9)
+        got = clone_out(env.test_rollout(actor, T_BITS, start=start, traj=True))
+        torch.cuda.synchronize()
+        ref = unfused_episode(orc, env, actor, start, T_BITS)
+        _cases[key] = dict(env=env, actor=actor, layers=layers, start=start, got=got, ref=ref,
+                           speed=speed, angle=angle)
+    return _cases[key]
+
+
+@pytest.mark.parametrize("n", [1, 97, 16421])
+@pytest.mark.parametrize("hidden,nh", [(200, 3), (256, 2)])
+def test_bitwise_vs_unfused_composition(nav, orc, hidden, nh, n):
+    """traj, final_state, reached, steps and best_distance equal the host loop of nav_act(mode=1)
+    -> nav_env_step bit for bit: one-row tile, partial tile, and the 64-row side of the block
+    height switch."""
+    c = bit_case(orc, hidden, nh, n)
+    got, ref = c["got"], c["ref"]
+    if n > 1:
+        # a condition on the inputs: some rows stop early, some run to the end
+        r = ref["reached"]
+        assert 0 < int(r.sum()) < n
+        assert int((ref["steps"] == 1).sum()) > 0
+    assert torch.equal(got["traj"], ref["traj"])
+    assert torch.equal(got["final_state"], ref["final_state"])
+    assert torch.equal(got["reached"].cpu(), ref["reached"])
+    assert torch.equal(got["steps"].cpu(), ref["steps"])
+    assert torch.equal(got["best_distance"].cpu(), ref["best_distance"])
+
+
+def test_outputs_are_what_traj_implies(nav, orc):
+    """reached / steps / best_distance / final_state recomputed on the CPU from traj and the
+    goals (orc.norm2, the threshold of params_struct()): equal, the doubles bit for bit."""
+    from nav._lib import params_struct
+    c = bit_case(orc, 200, 3, 97)
+    got = {k: v.cpu().numpy() for k, v in c["got"].items()}
+    goal = c["env"].goal.cpu().numpy()
+    thr = params_struct().goal_threshold
+    traj = got["traj"]
+    T, n = traj.shape[:2]
+    for e in range(n):
+        dist = norm2_rows(orc, traj[:, e] - goal[e])
+        hits = np.nonzero(dist <= thr)[0]
+        k = int(hits[0]) + 1 if len(hits) else T  # steps taken
+        assert got["reached"][e] == (1 if len(hits) else 0)
+        assert got["steps"][e] == k
+        assert got["best_distance"][e] == dist[:k].min()
+        assert np.array_equal(got["final_state"][e], traj[k - 1, e])
+        assert np.array_equal(traj[k - 1:, e], np.broadcast_to(traj[k - 1, e], (T - k + 1, 2)))
+
+
+def test_teacher_forced_step_parity(nav, orc):
+    """Every step of every env against an independent CPU step from the kernel's own previous
+    state: torch-CPU fp32 forward of f32(s - goal), orc.act_epilogue, orc.step; |traj[t] - next|
+    <= 3e-4 per component. The bound is derived: the action is pinned at 2e-4 per component
+    (test_act_vs_reference_golden), speed < 1 and a rotation turn that into at most 2e-4 * sqrt(2)
+    < 3e-4 of displacement. The n = 97 case's field, goals, starts and actor with goal_threshold 0,
+    so that no env stops and every (step, env) is a real step. Measured maximum on an MI355X:
+    see DESIGN.md (test episodes)."""
+    c = bit_case(orc, 200, 3, 97)
+    T, n = 8, 97
+    env = make_env(n, c["speed"], c["angle"], goal_threshold=0.0)
+    assert torch.equal(env.goal, c["env"].goal)
+    out = env.test_rollout(c["actor"], T, start=c["start"], traj=True)
+    traj = out["traj"].cpu().numpy()
+    assert int(out["reached"].sum()) == 0
+    goal = env.goal.cpu().numpy()
+    prev = c["start"].cpu().numpy()
+    worst = 0.0
+    for t in range(T):
+        x = torch.tensor((prev - goal).astype(np.float32))
+        h = x
+        for i, (W, b) in enumerate(c["layers"]):
+            h = torch.nn.functional.linear(h, W, b)
+            if i < len(c["layers"]) - 1:
+                h = torch.relu(h)
+        res = h.numpy()
+        for e in range(n):
+            a = orc.act_epilogue(prev[e], goal[e], res[e], 0, None)
+            nxt, _ = orc.step(c["speed"], c["angle"], prev[e], a)
+            worst = max(worst, float(np.abs(traj[t, e] - nxt).max()))
+        prev = traj[t]
+    print(f"teacher-forced max |traj - next| = {worst:.3e}")
+    assert worst <= 3e-4
+
+
+def test_homing_episode_vs_cpu_rollout(nav, orc):
+    """Constant field (speed 1, angle 0.5: rot = f32 pi, the baseline action points at the goal),
+    an all-zero actor (residual exactly 0), one goal, starts on a spiral: every env walks home in
+    1 to 17 steps, whole tiles leave early while row 96 runs on. Step counts exact, states and
+    best distances within 1e-9 of the CPU rollout (device dynamics is pinned to the oracle at
+    1e-11 per step)."""
+    from nav.mlp import DeviceMLP
+    n = 97
+    speed = np.full((100, 100), 1.0, np.float32)
+    angle = np.full((100, 100), 0.5, np.float32)
+    env = make_env(n, speed, angle)
+    g = np.array([8.0, 9.0])
+    env.goal.copy_(torch.tensor(g).expand(n, 2))
+    i = np.arange(n)
+    r, th = 5.5 + 0.85 * i, 0.1 + 1.3 * i / 96
+    start = g + r[:, None] * np.stack([np.cos(th), np.sin(th)], 1)
+    actor = DeviceMLP(2, 2, 64, 2, DEV)  # all parameters zero
+    actor.pack()
+    # the CPU rollout
+    dists, finals = [], []
+    margin = np.inf
+    for e in range(n):
+        s, ds = start[e].copy(), []
+        for _ in range(64):
+            s, _ = orc.step(speed, angle, s, np.clip(s - g, -5.0, 5.0))
+            ds.append(orc.norm2(s[0] - g[0], s[1] - g[1]))
+            margin = min(margin, abs(ds[-1] - 5.0))
+            if ds[-1] <= 5.0:
+                break
+        assert ds[-1] <= 5.0
+        dists.append(ds)
+        finals.append(s)
+    steps = np.array([len(d) for d in dists], np.int32)
+    # conditions on the inputs: no distance near the threshold, early tiles, a late row
+    assert margin > 1e-6
+    assert steps.min() == 1 and steps.max() == 17
+    assert steps[:32].max() <= 5 and steps[:64].max() <= 9 and steps[96] == 17
+    st = torch.tensor(start, device=DEV)
+    out = clone_out(env.test_rollout(actor, 24, start=st))
+    assert torch.all(out["reached"] == 1)
+    assert np.array_equal(out["steps"].cpu().numpy(), steps)
+    assert np.abs(out["final_state"].cpu().numpy() - np.array(finals)).max() <= 1e-9
+    out = clone_out(env.test_rollout(actor, 6, start=st))
+    want = steps <= 6
+    assert int(want.sum()) == 50
+    assert np.array_equal(out["reached"].cpu().numpy().astype(bool), want)
+    assert np.array_equal(out["steps"].cpu().numpy(), np.where(want, steps, 6))
+    best = np.array([min(d[:6]) for d in dists])
+    assert np.abs(out["best_distance"].cpu().numpy() - best).max() <= 1e-9
+
+
+def test_start_draw(nav, orc):
+    """start = NULL: env e starts at region_sample(region[e], u01(w.x, w.y), u01(w.z, w.w)), w =
+    philox(0, e, NAV_TAG_TEST = 6, episode): the first step equals the explicit-start run from the
+    CPU-derived starts bit for bit; the same episode repeats, another episode starts elsewhere."""
+    c = bit_case(orc, 200, 3, 97)
+    env, actor = c["env"], c["actor"]
+    region = env.region.cpu().numpy()
+
+    def u01(hi, lo):  # nav_device.h:38-40
+        return (float(hi >> 5) * 67108864.0 + float(lo >> 6)) / 9007199254740992.0
+
+    def starts(episode):
+        out = np.zeros((env.n, 2))
+        for e in range(env.n):
+            w = orc.philox([0, e, 6, episode], [env.p.seed_lo, env.p.seed_hi])
+            out[e] = orc.reset_u(region[e], u01(w[0], w[1]), u01(w[2], w[3]))
+        return out
+
+    firsts = {}
+    for episode in (0, 3):
+        drawn = clone_out(env.test_rollout(actor, 1, episode=episode, traj=True))
+        s0 = starts(episode)
+        assert np.all((s0[:, 0] >= region[:, 0]) & (s0[:, 0] <= region[:, 1]))
+        given = clone_out(env.test_rollout(actor, 1, start=torch.tensor(s0, device=DEV),
+                                           traj=True))
+        for k in drawn:
+            assert torch.equal(drawn[k], given[k]), k
+        again = env.test_rollout(actor, 1, episode=episode, traj=True)
+        for k in drawn:
+            assert torch.equal(drawn[k], again[k]), k
+        firsts[episode] = (s0, drawn["traj"][0].cpu().numpy())
+    assert np.all(np.any(firsts[0][0] != firsts[3][0], axis=1))
+    assert np.any(firsts[0][1] != firsts[3][1])
+
+
+def _equal_tree(a, b, path=""):
+    if isinstance(a, dict):
+        assert a.keys() == b.keys(), path
+        for k in a:
+            _equal_tree(a[k], b[k], f"{path}/{k}")
+    elif isinstance(a, (list, tuple)):
+        assert len(a) == len(b), path
+        for i, (x, y) in enumerate(zip(a, b)):
+            _equal_tree(x, y, f"{path}/{i}")
+    elif torch.is_tensor(a):
+        assert torch.equal(a, b), path
+    else:
+        assert a == b, path
+
+
+def test_evaluate_leaves_training_untouched(nav):
+    """Two equal trainers, 3 steps each, evaluate() on one, 2 more steps each: equal state_dicts.
+    evaluate() returns the documented dict; its success_rate is the mean of a direct
+    test_rollout's reached flags."""
+    from nav.trainer import VecTrainer
+
+    def trainer():
+        return VecTrainer(n_envs=256, hidden=64, n_hidden=2, batch=128, demos=False, seed=1234,
+                          device=DEV)
+
+    a, b = trainer(), trainer()
+    for _ in range(3):
+        a.step()
+        b.step()
+    ev = a.evaluate(max_steps=16)
+    assert set(ev) == {"n", "success_rate", "mean_steps_reached", "mean_best_distance",
+                       "max_best_distance", "max_steps", "episode"}
+    assert (ev["n"], ev["max_steps"], ev["episode"]) == (256, 16, 0)
+    direct = a.env.test_rollout(a.td3.actor_network, 16, episode=0)
+    assert ev["success_rate"] == direct["reached"].float().mean().item()
+    assert ev["max_best_distance"] == direct["best_distance"].max().item()
+    assert ev["mean_best_distance"] <= ev["max_best_distance"]
+    for _ in range(2):
+        a.step()
+        b.step()
+    torch.cuda.synchronize()
+    _equal_tree(a.state_dict(), b.state_dict())

@@ -1,0 +1,51 @@
+"""Score a vectorised trainer's policy as robot-learning.py's testing mode does: one greedy test
+episode per env (VecTrainer.evaluate -> nav_test_rollout, one launch), printed as one JSON line.
+
+python tools/evaluate.py --checkpoint run.pt
+python tools/evaluate.py --n-envs 4096 --hidden 256 --n-hidden 2 --seed 7 --train-steps 200
+"""
+import argparse
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, ".."))
+sys.path.insert(0, os.path.join(HERE, "..", "residual-td3-robot-navigation_amd"))
+
+
+def main():
+    from nav import config as K
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--checkpoint", default=None, help="a VecTrainer.save() file")
+    ap.add_argument("--n-envs", type=int, default=4096)
+    ap.add_argument("--hidden", type=int, default=256)
+    ap.add_argument("--n-hidden", type=int, default=2)
+    ap.add_argument("--batch", type=int, default=None, help="default: n_envs / 2")
+    ap.add_argument("--seed", type=int, default=K.RANDOM_SEED)
+    ap.add_argument("--no-demos", action="store_true")
+    ap.add_argument("--train-steps", type=int, default=0)
+    ap.add_argument("--max-steps", type=int, default=K.TEST_TIMEOUT * K.UPDATE_RATE)
+    ap.add_argument("--episode", type=int, default=0)
+    args = ap.parse_args()
+    import torch
+    from nav._lib import require_gpu
+    from nav.trainer import VecTrainer
+    require_gpu()
+    if args.checkpoint:
+        tr = VecTrainer.load(args.checkpoint)
+    else:
+        tr = VecTrainer(n_envs=args.n_envs, hidden=args.hidden, n_hidden=args.n_hidden,
+                        batch=args.batch or max(args.n_envs // 2, 1), seed=args.seed,
+                        envs_per_group=min(1024, args.n_envs), demos=not args.no_demos)
+    for _ in range(args.train_steps):
+        tr.step()
+    res = tr.evaluate(max_steps=args.max_steps, episode=args.episode)
+    torch.cuda.synchronize()
+    res["train_steps"] = tr.steps
+    # strict JSON: a NaN (no env reached) prints as null
+    print(json.dumps({k: None if isinstance(v, float) and v != v else v for k, v in res.items()}))
+
+
+if __name__ == "__main__":
+    main()
