@@ -18,8 +18,9 @@ namespace {
 // 256 workgroups (one per CU, 2 waves per SIMD) fill the chip, so the slabs are 4-8 MB per
 // launch and the reduce reads 8-16 slabs.
 // 2-hidden-layer networks with whole tiles (the bench shape) take the factored path
-// (wgrad_rows_fact: the ReLU bit as an exact bf16 A operand, Wo applied after the sum, tn = 128
-// for d_out = 1). Every other shape takes the f32 MFMA path below (tn = 64).
+// (wgrad_rows_fact: the ReLU bit as an exact bf16 A operand, Wo applied after the sum; for
+// d_out = 1 the tile is 256 x 32 at hp 256 and 128 x 64 at hp 128). Every other shape takes the
+// f32 MFMA path below (tn = 64).
 // Operands come straight from registers, no panel staging and no barrier in the row loop: for
 // the batch rows (2 per MFMA step: lane half h = row parity) every lane forms its own A element
 // P[row][n0 + 32 i + lane] and B element Q[row][k0 + 32 j + lane]. P = dz of the top hidden
@@ -40,8 +41,9 @@ struct WgradArgs {
     const uint16_t* masks[2];  // the forward's ReLU bit image
     float* slabs[2];        // [splits][(nh-1) hp hp]
     int splits;
-    int TT;                 // 64-wide tiles across hp (the k side of a tile)
-    int tn;                 // tile height on the n side: 64, or 128 (wgrad_tile_fact, d_out = 1)
+    int tk;                 // tile width on the k side: 64, or 32 (the 256 x 32 factored form)
+    int TT;                 // tk-wide tiles across hp (the k side of a tile)
+    int tn;                 // tile height on the n side: 64, or 128 / 256 (wgrad_tile_fact)
     int TN;                 // tn-high tiles across hp
     int n_hid;              // tile jobs per network = (nh - 1) * TN * TT
     int fact;               // 1: the factored-Wo path (wgrad_tile_fact) for every tile
@@ -84,14 +86,33 @@ constexpr int WG_STAGE_FLOATS = WG_CHUNK * 6;  // one slot; 2 slots per wave (do
 inline size_t wgrad_lds_bytes() {
     return ((size_t)WG_WAVES * WG_TILE * WG_TILE + (size_t)WG_WAVES * 2 * WG_STAGE_FLOATS) * 4;
 }
-// The factored path's tile height: 128 rows of n for d_out = 1 when hp allows (NI = 4 column
-// tiles per wave at 128 accumulator registers), else 64. The path itself needs a 2-hidden-layer
-// network with whole 64 x 64 tiles.
+// The factored path's tile: for d_out = 1 a wave holds 128 accumulator registers, as 256 (n) x 32
+// (k) when hp % 256 == 0 (NI = 8 column tiles of n, one 32-column half of k: every B operand
+// Q = g relu(h_0) is formed once per launch, where two 128 x 64 tiles with the same k0 formed it
+// twice), as 128 x 64 (NI = 4, two halves) when hp % 128 == 0, else 64 x 64. The path itself needs
+// a 2-hidden-layer network with whole 64 x 64 tiles. -DNAV_WGRAD_FACT_WIDE=0 (A/B only) keeps
+// 128 x 64 at hp % 256 == 0.
+#ifndef NAV_WGRAD_FACT_WIDE
+#define NAV_WGRAD_FACT_WIDE 1
+#endif
 __host__ __device__ inline bool wgrad_fact_ok(int hp, int n_hidden) {
     return n_hidden == 2 && hp % WG_TILE == 0;
 }
-__host__ __device__ inline int wgrad_tile_n(int d_out, int hp, int n_hidden) {
-    return wgrad_fact_ok(hp, n_hidden) && d_out == 1 && hp % 128 == 0 ? 128 : WG_TILE;
+// the tile shape and the tile jobs per network of a launch: the one source for the grid
+// (nav_mlp_wgrad), the split count (nav_mlp_wgrad_splits) and the job decode (wgrad_job)
+struct WgradTiling {
+    int tn, tk, TN, TT, jobs;
+};
+inline WgradTiling wgrad_tiling(int d_out, int hp, int n_hidden) {
+    WgradTiling t;
+    const bool f1 = wgrad_fact_ok(hp, n_hidden) && d_out == 1;
+    const bool wide = NAV_WGRAD_FACT_WIDE && f1 && hp % 256 == 0;
+    t.tn = wide ? 256 : f1 && hp % 128 == 0 ? 128 : WG_TILE;
+    t.tk = wide ? 32 : WG_TILE;
+    t.TN = (hp + t.tn - 1) / t.tn;
+    t.TT = (hp + t.tk - 1) / t.tk;
+    t.jobs = (n_hidden > 1 ? n_hidden - 1 : 0) * t.TN * t.TT;
+    return t;
 }
 
 // rows [r_lo, r_hi) of one wave into acc (tile n0.., k0.. of layer L of net y)
@@ -551,49 +572,51 @@ NAV_DEV void wgrad_rows_mfma(const WgradArgs& a, int y, int n0, int k0, int64_t 
 // power of two (h_0 per column k into [2^6, 2^7) through the layer-0 constants, g_d per wave into
 // [2^7, 2^8) from the wave's max |g_d|) and cut into two fp16 planes, so the product carries f32
 // accuracy with 2 MFMAs per 16-deep k step and 32 x 32 tile (the three-plane bf16 form: 3), and
-// nothing per element on the n side. That frees a wave to own NI = 4 column tiles of n
-// (128 x 64) at D = 1 — the twin critics — for 128 accumulator registers.
+// nothing per element on the n side. That frees a wave to own NI * KH = 8 blocks of 32 x 32 at
+// D = 1 — the twin critics — for 128 accumulator registers: all 8 along n (256 x 32) at hp 256,
+// so that no other workgroup of the launch forms the same Q; 128 x 64 at hp 128.
 
 
 // GV: dy rows packed (ld_dy = D) and 16-B aligned (float4 loads at fixed offsets); XV: x rows of 4
 // floats, 16-B aligned (one float4 load per row). Both are launch-uniform: the full-tile loop is
 // compiled per form, with running row pointers and no per-tile branch on the layout.
-template <int NI, int D, bool GV, bool XV>
+// KH: 32-column halves of the k side per wave (tile NI*32 x KH*32; NI * KH = 8 at D = 1).
+template <int NI, int D, int KH, bool GV, bool XV>
 NAV_DEV void wgrad_rows_fact(const WgradArgs& a, int y, int n0, int k0, int64_t r_lo,
-                             int64_t r_hi, const char* tab, f32x16 (&out)[NI][2]) {
+                             int64_t r_hi, const char* tab, f32x16 (&out)[NI][KH]) {
     const MlpDev& net = a.net[y];
     const int hp = net.hp, d_in = net.d_in;
     const int lane = threadIdx.x & 63, h = lane >> 5, l32 = lane & 31;
     const int64_t M = a.M;
     const int NTm = hp >> 5;
-    f32x16 acc[D][NI][2];
+    f32x16 acc[D][NI][KH];
 #pragma unroll
     for (int d = 0; d < D; ++d)
 #pragma unroll
         for (int i = 0; i < NI; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < KH; ++j)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[d][i][j][e] = 0.f;
     // h_0 = relu(x . W0^T + b0) by f32 MFMAs in the C layout, where lane (l32, h) register e
     // holds row acc_row(e, h) of column l32. Constant B operands: W0 columns (k = h, then 2 + h),
     // and the bias through a K = 2 MFMA of (1, 0) x (b, 0), so the C tile starts at b exactly and
     // h_0 accumulates in layer0_unit's order b + x0 w0 + x1 w1 + x2 w2 + x3 w3
-    float w0b[2][2], bob[2];
+    float w0b[KH][2], bob[KH];
     {
         const float* W0 = net.params + net.w_off[0];
         const float* bb = net.params + net.b_off[0];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
+        for (int j = 0; j < KH; ++j) {
             const int c = k0 + 32 * j + l32;
             w0b[j][0] = h < d_in ? W0[c * d_in + h] : 0.f;
             w0b[j][1] = 2 + h < d_in ? W0[c * d_in + 2 + h] : 0.f;
             bob[j] = h == 0 ? bb[c] : 0.f;
         }
     }
-    int eh[2], eg[D];  // the fp16 operand scales (below, under the first tile's loads)
+    int eh[KH], eg[D];  // the fp16 operand scales (below, under the first tile's loads)
     float sg[D];
-    float bcj[2];      // the scaled bias of the lane's column per half (below, with the scales)
+    float bcj[KH];     // the scaled bias of the lane's column per half (below, with the scales)
     const bool x23 = d_in > 2;
     const size_t mstride = (size_t)NTm * 64;
     const uint16_t* mp = a.masks[y] + (size_t)mask_rowtiles(M) * mstride +  // layer 1's bits
@@ -603,9 +626,19 @@ NAV_DEV void wgrad_rows_fact(const WgradArgs& a, int y, int n0, int k0, int64_t 
     const int xk0 = h < d_in ? h : 0, xk1 = 2 + h < d_in ? 2 + h : 0;
     // the tile's own A operands (x row of lane l32, inputs k = h and 2 + h) and the lane's NI
     // mask words; the main loop keeps the next full tile's in flight
+    // (NI = 8: two 16-bit mask words per register, tile 2u in the low half, so the current and the
+    // prefetched set hold 8 registers instead of 16; byte 2 (i & 1) + s2 of m[i >> 1] is k step s2)
+    constexpr bool MP = NI == 8;
+    constexpr int NM = MP ? NI / 2 : NI;
     struct Raw {
         float x0, x1;
-        uint32_t m[NI];
+        uint32_t m[NM];
+    };
+    auto load_masks = [&](const uint16_t* m, Raw& v) {
+#pragma unroll
+        for (int u = 0; u < NM; ++u)
+            v.m[u] = MP ? (uint32_t)m[2 * u * 64] | ((uint32_t)m[(2 * u + 1) * 64] << 16)
+                        : (uint32_t)m[u * 64];
     };
     // the x row as one 16-B load when it is 4 aligned floats (both lane halves read the row)
     const bool xrow4 = d_in == 4 && (ld_in & 3) == 0 && (((uintptr_t)(a.in + a.in_col)) & 15) == 0;
@@ -620,9 +653,7 @@ NAV_DEV void wgrad_rows_fact(const WgradArgs& a, int y, int n0, int k0, int64_t 
             v.x0 = x[xk0];
             v.x1 = x[xk1];
         }
-        const uint16_t* m = mp + (size_t)((rt - r_lo) >> 5) * mstride;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) v.m[i] = m[i * 64];
+        load_masks(mp + (size_t)((rt - r_lo) >> 5) * mstride, v);
     };
     // one 32-row tile: h_0 by the f32 MFMAs, Q_d = relu(h_0) g_d split per k step, 2 MFMAs per
     // (i, j, d) and step. gs[s2][d][t]: g_d (scaled) of the row of register e = 8 s2 + t
@@ -630,7 +661,7 @@ NAV_DEV void wgrad_rows_fact(const WgradArgs& a, int y, int n0, int k0, int64_t 
         const float x0 = h < d_in ? cur.x0 : 0.f, x1 = 2 + h < d_in ? cur.x1 : 0.f;
         // one 32-column half j of the k side at a time (16 registers of h_0 live)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
+        for (int j = 0; j < KH; ++j) {
             // the C operand starts at the column's scaled bias (exactly what the K = 2 bias MFMA
             // of (1, 0) x (b, 0) produced), set by VALU: one f32 MFMA fewer per half and tile
             f32x16 Z;
@@ -654,7 +685,8 @@ NAV_DEV void wgrad_rows_fact(const WgradArgs& a, int y, int n0, int k0, int64_t 
                         // the fragment of byte s2 of the mask word, read from the table right
                         // before its 3 MFMAs (the opaque offset keeps the compiler from holding
                         // all NI x 2 fragments live across the passes over j)
-                        uint32_t ta = (s2 == 0 ? cur.m[i] << 4 : cur.m[i] >> 4) & 0xFF0u;
+                        uint32_t ta = MP ? ((cur.m[i >> 1] >> (16 * (i & 1) + 8 * s2)) & 0xFFu) << 4
+                                         : (s2 == 0 ? cur.m[i] << 4 : cur.m[i] >> 4) & 0xFF0u;
                         asm volatile("" : "+v"(ta));
                         const f16x8 pi = *reinterpret_cast<const f16x8*>(tab + ta);
                         acc[d][i][j] = mfma_h(pi, sq.l, acc[d][i][j]);
@@ -721,8 +753,7 @@ NAV_DEV void wgrad_rows_fact(const WgradArgs& a, int y, int n0, int k0, int64_t 
             v.x0 = xq[xk0];
             v.x1 = xq[xk1];
         }
-#pragma unroll
-        for (int i = 0; i < NI; ++i) v.m[i] = mq[i * 64];
+        load_masks(mq, v);
         if (GPF) load_g_at(gq, gs);
         xq += xstep;
         mq += mstride;
@@ -748,7 +779,7 @@ NAV_DEV void wgrad_rows_fact(const WgradArgs& a, int y, int n0, int k0, int64_t 
         // per 32-column half (wave-uniform, scalar registers: the 128-accumulator program has no
         // vector register to spare)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
+        for (int j = 0; j < KH; ++j) {
             eh[j] = __builtin_amdgcn_readfirstlane(
                 pow2_exp_to(wave_max_abs(h0_bound(X, w0b[j][0], w0b[j][1], bob[j])), 7));
             // (the sum capped at 2^120: Z = h_0 2^eh stays finite for every finite h_0 bound)
@@ -796,6 +827,9 @@ NAV_DEV void wgrad_rows_fact(const WgradArgs& a, int y, int n0, int k0, int64_t 
     const float* Wo = net.params + net.w_off[net.n_hidden];
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
+        // NI = 8: two column tiles' Wo loads at a time (all 32 float4 loads hoisted above the
+        // products cost 17 spilled registers next to the 128 accumulators)
+        if (NI == 8 && i > 0 && i % 2 == 0) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int n = n0 + 32 * i + 8 * q + 4 * h;
@@ -809,7 +843,7 @@ NAV_DEV void wgrad_rows_fact(const WgradArgs& a, int y, int n0, int k0, int64_t 
             for (int t = 0; t < 4; ++t) {
                 const int e = 4 * q + t;
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
+                for (int j = 0; j < KH; ++j) {
                     const float w0 = (t == 0 ? wv[0].x : t == 1 ? wv[0].y : t == 2 ? wv[0].z : wv[0].w) * 0.5f;
                     float v = w0 * ldexpf(acc[0][i][j][e], -(eh[j] + eg[0]));
                     if (D > 1) {
@@ -824,18 +858,18 @@ NAV_DEV void wgrad_rows_fact(const WgradArgs& a, int y, int n0, int k0, int64_t 
     }
 }
 
-// The NI tiles of each wave summed across the 8 waves through LDS (R slots of NI*32 x 64 floats
-// in 128 KB: waves w and w + R share slot w % R, in wave order) and written as one slab tile.
+// The NI x KH blocks of each wave summed across the 8 waves through LDS (R slots of NI*32 x KH*32
+// floats in 128 KB: waves w and w + R share slot w % R, in wave order) and written as one slab tile.
 // Slot layout: per 32 x 32 block (i, j) and lane, the lane's 16 accumulator values contiguous
 // (16-B LDS accesses, 4 per block instead of 16 single-dword ones), the 4 chunks of a lane
 // rotated by (lane >> 2) & 3 so the 8 lanes of one LDS cycle hit distinct banks. The final pass
 // gives wave w the blocks w, w + 8, ...: 16 values per lane summed over the slots in slot order
 // (the same order as p_0 + p_R + p_1 + ... of a row-major slot), each stored to 32 consecutive
 // columns of a slab row per lane half.
-template <int NI>
+template <int NI, int KH>
 NAV_DEV void wgrad_reduce_write(const WgradArgs& a, int y, int split, int L, int n0, int k0,
-                                const f32x16 (&acc)[NI][2], float* red) {
-    constexpr int T = NI * 32 * WG_TILE;
+                                const f32x16 (&acc)[NI][KH], float* red) {
+    constexpr int T = NI * 32 * 32 * KH;
     constexpr int R = (WG_WAVES * WG_TILE * WG_TILE) / T < WG_WAVES
                           ? (WG_WAVES * WG_TILE * WG_TILE) / T : WG_WAVES;
     const MlpDev& net = a.net[y];
@@ -849,8 +883,8 @@ NAV_DEV void wgrad_reduce_write(const WgradArgs& a, int y, int split, int L, int
 #pragma unroll
             for (int i = 0; i < NI; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    float4* p = mine + ((i * 2 + j) * 64 + lane) * 4;
+                for (int j = 0; j < KH; ++j) {
+                    float4* p = mine + ((i * KH + j) * 64 + lane) * 4;
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         float4 v = make_float4(acc[i][j][4 * c], acc[i][j][4 * c + 1],
@@ -867,8 +901,8 @@ NAV_DEV void wgrad_reduce_write(const WgradArgs& a, int y, int split, int L, int
     }
     float* o = a.slabs[y] + (int64_t)split * hidden_w_count(net) + (int64_t)(L - 1) * hp * hp;
     const float4* slots = reinterpret_cast<const float4*>(red);
-    for (int b = wv; b < NI * 2; b += WG_WAVES) {
-        const int i = b >> 1, j = b & 1;
+    for (int b = wv; b < NI * KH; b += WG_WAVES) {
+        const int i = b / KH, j = b % KH;
         float v[16];
 #pragma unroll
         for (int w = 0; w < R; ++w) {
@@ -908,7 +942,7 @@ NAV_DEV TileJob wgrad_job(const WgradArgs& a, int b, int total) {
     t.split = grp % a.splits;
     t.L = t.job / (TN * TT) + 1;
     t.n0 = ((t.job % (TN * TT)) / TT) * a.tn;
-    t.k0 = (t.job % TT) * WG_TILE;
+    t.k0 = (t.job % TT) * a.tk;
     return t;
 }
 
@@ -928,7 +962,7 @@ NAV_DEV void wave_rows(const WgradArgs& a, int split, int wv, int64_t skew, int6
     r_hi = r_lo + len < s_hi ? r_lo + len : s_hi;
 }
 
-template <int NI, int D>
+template <int NI, int D, int KH>
 NAV_DEV void wgrad_tile_fact(const WgradArgs& a, const TileJob& t, float* smem, uint4* tab) {
     WG_MARK(0, 0);
     // the bits -> A fragment table (a static LDS array: its address is a constant, so a fragment
@@ -946,17 +980,17 @@ NAV_DEV void wgrad_tile_fact(const WgradArgs& a, const TileJob& t, float* smem, 
     WG_MARK(0, 1);
     int64_t r_lo, r_hi;
     wave_rows(a, t.split, wave_id(), a.skew, r_lo, r_hi);
-    f32x16 out[NI][2];
+    f32x16 out[NI][KH];
     const char* tb = reinterpret_cast<const char*>(tab);
     const bool gv = a.ld_dy == D && ((uintptr_t)a.dy[t.y] & 15) == 0;
     const bool xv = a.net[t.y].d_in == 4 && (a.ld_in & 3) == 0 &&
                     ((uintptr_t)(a.in + a.in_col) & 15) == 0;
-    if (gv && xv) wgrad_rows_fact<NI, D, true, true>(a, t.y, t.n0, t.k0, r_lo, r_hi, tb, out);
-    else if (gv) wgrad_rows_fact<NI, D, true, false>(a, t.y, t.n0, t.k0, r_lo, r_hi, tb, out);
-    else if (xv) wgrad_rows_fact<NI, D, false, true>(a, t.y, t.n0, t.k0, r_lo, r_hi, tb, out);
-    else wgrad_rows_fact<NI, D, false, false>(a, t.y, t.n0, t.k0, r_lo, r_hi, tb, out);
+    if (gv && xv) wgrad_rows_fact<NI, D, KH, true, true>(a, t.y, t.n0, t.k0, r_lo, r_hi, tb, out);
+    else if (gv) wgrad_rows_fact<NI, D, KH, true, false>(a, t.y, t.n0, t.k0, r_lo, r_hi, tb, out);
+    else if (xv) wgrad_rows_fact<NI, D, KH, false, true>(a, t.y, t.n0, t.k0, r_lo, r_hi, tb, out);
+    else wgrad_rows_fact<NI, D, KH, false, false>(a, t.y, t.n0, t.k0, r_lo, r_hi, tb, out);
     WG_MARK(0, 5);
-    wgrad_reduce_write<NI>(a, t.y, t.split, t.L, t.n0, t.k0, out, smem);
+    wgrad_reduce_write<NI, KH>(a, t.y, t.split, t.L, t.n0, t.k0, out, smem);
     WG_MARK(0, 6);
 }
 
@@ -997,7 +1031,7 @@ NAV_DEV void wgrad_tile(const WgradArgs& a, const TileJob& t, float* smem) {
     }
     // the 8 partial tiles meet in LDS, summed in wave order
     WG_MARK(1, 5);
-    wgrad_reduce_write<2>(a, y, split, L, n0, k0, acc, red);
+    wgrad_reduce_write<2, 2>(a, y, split, L, n0, k0, acc, red);
     WG_MARK(1, 6);
 }
 
@@ -1011,11 +1045,11 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad_gen(WgradArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     wgrad_tile<true>(a, wgrad_job(a, blockIdx.x, gridDim.x), smem);
 }
-template <int NI, int D>
+template <int NI, int D, int KH>
 __global__ __launch_bounds__(WG_THREADS) void k_wgrad_fact(WgradArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ uint4 tab[256];
-    wgrad_tile_fact<NI, D>(a, wgrad_job(a, blockIdx.x, gridDim.x), smem, tab);
+    wgrad_tile_fact<NI, D, KH>(a, wgrad_job(a, blockIdx.x, gridDim.x), smem, tab);
 }
 
 // ---------------- optimizer / target update, refreshing the packed images ----------------
@@ -1475,10 +1509,7 @@ int32_t nav_mlp_wgrad_splits(int32_t n_nets, int32_t d_out, int32_t hidden_pad, 
         hidden_pad > 256 || (hidden_pad & 31) || n_hidden < 1 || M < 0)
         return NAV_EINVAL;
     if (n_hidden < 2) return 1;
-    const int TT = (hidden_pad + WG_TILE - 1) / WG_TILE;
-    const int tn = wgrad_tile_n(d_out, hidden_pad, n_hidden);
-    const int TN = (hidden_pad + tn - 1) / tn;
-    const int64_t jobs = (int64_t)n_nets * (n_hidden - 1) * TN * TT;
+    const int64_t jobs = (int64_t)n_nets * wgrad_tiling(d_out, hidden_pad, n_hidden).jobs;
     // WG_TOTAL workgroups (256: one 8-wave workgroup per CU), at least 512 rows per split
     int64_t s = WG_TOTAL / jobs;
     const int64_t by_rows = (M + 511) / 512;
@@ -1514,10 +1545,12 @@ static int wgrad_args(const nav_mlp* nets, int32_t n_nets, int64_t M, const floa
     a.ld_dy = ld_dy;
     a.splits = splits;
     const int hp = a.net[0].hp, nh = a.net[0].n_hidden;
-    a.TT = (hp + WG_TILE - 1) / WG_TILE;
-    a.tn = wgrad_tile_n(a.net[0].d_out, hp, nh);
-    a.TN = (hp + a.tn - 1) / a.tn;
-    a.n_hid = (nh - 1) * a.TN * a.TT;
+    const WgradTiling tl = wgrad_tiling(a.net[0].d_out, hp, nh);
+    a.tk = tl.tk;
+    a.TT = tl.TT;
+    a.tn = tl.tn;
+    a.TN = tl.TN;
+    a.n_hid = tl.jobs;
     // the factored path for the critics (d_out = 1); the actor's d_out = 2 would need two
     // accumulator sets and two splits per element (measured slower than wgrad_rows_mfma: 40 vs
     // 34 us at 2x256 on bf16, profiles/r04c; on the fp16 split 31.9 vs 25.4 us, r06r)
@@ -1530,7 +1563,8 @@ static int wgrad_args(const nav_mlp* nets, int32_t n_nets, int64_t M, const floa
     // whole 32-row tiles moved to the first wave of each SIMD pair, per 256 rows of a wave
     // (tools/wgrad_bench.py, profiles/r05ad_ab_wgrad_skew.txt: 0 / 32 / 64 / 96 rows for the
     // factored kernel -> 32.5 / 32.0 / 31.8 / 33.0 us, 0 / 64 / 96 / 128 for the operand path ->
-    // 27.4 / 27.4 / 27.1 / 26.8 us)
+    // 27.4 / 27.4 / 27.1 / 26.8 us; the 256 x 32 factored form re-tuned, r07c_ab_wgrad_skew.txt:
+    // 0 / 32 / 64 / 96 -> 26.6 / 26.4 / 26.3 / 26.5 us, 64 kept)
     a.skew = (a.per_wave / 256) * (a.fact ? NAV_WG_SKEW_FACT : NAV_WG_SKEW_OPND);
     if ((int64_t)n_nets * a.n_hid * splits > ((int64_t)1 << 30)) return NAV_EINVAL;
     return 0;
@@ -1550,7 +1584,9 @@ int nav_mlp_wgrad(const nav_mlp* nets, int32_t n_nets, int64_t M, const float* i
     // the factored kernel: its 4 KB fragment table is static, the dynamic part the reduce slots
     const size_t lds = a.fact ? (size_t)WG_WAVES * WG_TILE * WG_TILE * 4 : wgrad_lds_bytes();
     // >= 3 hidden layers: no tile is both the top and the first layer (no operand path)
-    void (*k)(WgradArgs) = a.fact                  ? (a.tn == 128 ? k_wgrad_fact<4, 1> : k_wgrad_fact<2, 1>)
+    void (*k)(WgradArgs) = a.fact                  ? (a.tn == 256   ? k_wgrad_fact<8, 1, 1>
+                                                      : a.tn == 128 ? k_wgrad_fact<4, 1, 2>
+                                                                    : k_wgrad_fact<2, 1, 2>)
                            : a.net[0].n_hidden >= 3 ? k_wgrad_gen
                                                     : k_wgrad;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k),

@@ -3,7 +3,12 @@
 #   tools/build_variant.sh NAME learner|env|mlpN "-DFOO=1 ..."  (mlpN: the row kernels of hidden
 #   width 32*N; mlp8 = 256; mlp0 = the row kernels' C-ABI object)
 # -> abl/libnavenv_NAME.so (bind it with python tools/withlib.py abl/libnavenv_NAME.so SCRIPT ...)
+# The learner unit's knobs: -DNAV_WGRAD_FACT_WIDE=0 (k_wgrad_fact as 128 x 64 wave tiles at hp 256
+# instead of 256 x 32), -DNAV_WG_SKEW_FACT=R / -DNAV_WG_SKEW_OPND=R (rows moved to the first wave of
+# a SIMD pair per 256 rows), -DNAV_WGRAD_TRACE (tools/wgrad_trace.py). WIDE=0 as the unit name is
+# short for the first:  tools/build_variant.sh narrow WIDE=0
 set -eu
+if [ "${2:-}" = "WIDE=0" ]; then set -- "$1" learner "-DNAV_WGRAD_FACT_WIDE=0 ${3:-}"; fi
 cd "$(dirname "$0")/.."
 name=$1; unit=$2; flags=$3
 P=residual-td3-robot-navigation_amd
