@@ -601,6 +601,31 @@ void orc_set_threads(int n) {
 #endif
 }
 
+void orc_vec_agent_step_batch_out(const orc_params_t* p, const float* speed, const float* angle,
+                                  const double* demo, int64_t m, int64_t n, double* state,
+                                  const double* goal, const double* region, double* hist,
+                                  uint32_t* meta, int32_t* plan_index, int32_t* path_length,
+                                  int32_t* episodes, double* noise_scale, const double* action,
+                                  double* next_out, float* rows, int64_t cap, int64_t base,
+                                  int64_t env0, const int64_t* idx_start, const int32_t* idx_cand,
+                                  int32_t* flags_out, double* reward_out) {
+    /* hist here is [n][5][2] (env-major; the device layout differs, the values do not);
+     * idx_start / idx_cand (nullable): the demo set's orc_demo_index_build index;
+     * flags_out / reward_out (nullable, [n]): each tick's return value and f64 reward */
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+    for (int64_t e = 0; e < n; ++e) {
+        int64_t slot = (base + e) % cap;
+        int fl = tick_impl(p, speed, angle, demo, m, idx_start, idx_cand, (uint32_t)(env0 + e),
+                           state + 2 * e, goal + 2 * e, region + 4 * e, hist + 10 * e, meta + e,
+                           plan_index + e, path_length + e, episodes + e, noise_scale + e,
+                           action + 2 * e, next_out + 2 * e, rows + 8 * slot,
+                           reward_out ? reward_out + e : NULL, NULL);
+        if (flags_out) flags_out[e] = fl;
+    }
+}
+
 void orc_vec_agent_step_batch(const orc_params_t* p, const float* speed, const float* angle,
                               const double* demo, int64_t m, int64_t n, double* state,
                               const double* goal, const double* region, double* hist,
@@ -608,17 +633,56 @@ void orc_vec_agent_step_batch(const orc_params_t* p, const float* speed, const f
                               int32_t* episodes, double* noise_scale, const double* action,
                               double* next_out, float* rows, int64_t cap, int64_t base,
                               int64_t env0, const int64_t* idx_start, const int32_t* idx_cand) {
-    /* hist here is [n][5][2] (env-major; the device layout differs, the values do not);
-     * idx_start / idx_cand (nullable): the demo set's orc_demo_index_build index */
+    orc_vec_agent_step_batch_out(p, speed, angle, demo, m, n, state, goal, region, hist, meta,
+                                 plan_index, path_length, episodes, noise_scale, action, next_out,
+                                 rows, cap, base, env0, idx_start, idx_cand, NULL, NULL);
+}
+
+/* ---- the product path's in-kernel Philox streams, batched. Each restates the device code's
+ * counter layout (include/navenv.h:39-41: ctr = (c0, c1, tag, c3), key = (seed_lo, seed_hi)) and
+ * its transform of the four output words. */
+enum { TAG_SAMPLE = 4, TAG_TNOISE = 5 };
+
+/* exploration noise of every env at vector step `step`: z [n][2] f64, the Box-Muller pair of
+ * philox(0, env, TAG_NOISE, step) (mlp_kernels.hip:1134 nav_act_tick, :1231 nav_act; gauss_pair
+ * nav_device.h:93-98) = orc_vec_noise_one for env 0 .. n-1 */
+void orc_vec_noise(const orc_params_t* p, int64_t n, uint32_t step, double* z) {
 #ifdef _OPENMP
 #pragma omp parallel for schedule(static)
 #endif
-    for (int64_t e = 0; e < n; ++e) {
-        int64_t slot = (base + e) % cap;
-        tick_impl(p, speed, angle, demo, m, idx_start, idx_cand, (uint32_t)(env0 + e),
-                  state + 2 * e, goal + 2 * e, region + 4 * e, hist + 10 * e, meta + e,
-                  plan_index + e, path_length + e, episodes + e, noise_scale + e, action + 2 * e,
-                  next_out + 2 * e, rows + 8 * slot, NULL, NULL);
+    for (int64_t e = 0; e < n; ++e) orc_vec_noise_one(p, (uint32_t)e, step, z + 2 * e);
+}
+
+/* replay sample indices of one batch: row b reads ring row (philox(b, 0, TAG_SAMPLE, ctr).x *
+ * size) >> 32, `size` the ring's fill (sample_row, mlp_kernels.hip:1725-1733;
+ * learner_kernels.hip:1422) */
+void orc_sample_indices(const orc_params_t* p, int64_t B, int64_t size, uint32_t ctr,
+                        int64_t* out) {
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+    for (int64_t b = 0; b < B; ++b) {
+        uint32_t w[4];
+        philox_words(p, (uint32_t)b, 0u, TAG_SAMPLE, ctr, w);
+        out[b] = (int64_t)(((uint64_t)w[0] * (uint64_t)size) >> 32);
+    }
+}
+
+/* target-policy smoothing draws of one batch: eps [B][2] f32 = the Box-Muller pair of
+ * philox(row, 0, TAG_TNOISE, ctr) rounded to f32, the value the kernels multiply by policy_noise
+ * and clamp (mlp_kernels.hip:1213-1218 OUT_TARGET, :1869-1873 k_td3_critic_rows) */
+void orc_smoothing_noise(const orc_params_t* p, int64_t B, uint32_t ctr, float* eps) {
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+    for (int64_t r = 0; r < B; ++r) {
+        uint32_t w[4];
+        philox_words(p, (uint32_t)r, 0u, TAG_TNOISE, ctr, w);
+        double u1 = orc_u01(w[0], w[1]), u2 = orc_u01(w[2], w[3]);
+        double rad = sqrt(-2.0 * log(1.0 - u1));
+        double th = 6.283185307179586 * u2;
+        eps[2 * r] = (float)(rad * cos(th));
+        eps[2 * r + 1] = (float)(rad * sin(th));
     }
 }
 

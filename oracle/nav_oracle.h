@@ -115,6 +115,26 @@ void orc_vec_agent_step_batch(const orc_params_t* p, const float* speed, const f
                               double* next_state_out, float* replay_rows, int64_t replay_cap,
                               int64_t replay_base, int64_t env0 /* global index of env 0 */,
                               const int64_t* idx_start, const int32_t* idx_cand /* nullable */);
+/* the same, with each tick's flags (orc_vec_agent_tick's return value) and f64 reward written to
+ * flags_out / reward_out [n] (both nullable) */
+void orc_vec_agent_step_batch_out(const orc_params_t* p, const float* speed, const float* angle,
+                                  const double* demo_xy, int64_t m, int64_t n, double* state,
+                                  const double* goal, const double* region, double* hist,
+                                  uint32_t* meta, int32_t* plan_index, int32_t* path_length,
+                                  int32_t* episodes, double* noise_scale, const double* action,
+                                  double* next_state_out, float* replay_rows, int64_t replay_cap,
+                                  int64_t replay_base, int64_t env0, const int64_t* idx_start,
+                                  const int32_t* idx_cand, int32_t* flags_out, double* reward_out);
+
+/* The product path's in-kernel Philox streams, batched (ctr = (c0, c1, tag, c3), key = seed):
+ * exploration noise z [n][2] of vector step `step` (tag 3, ctr (0, env, 3, step)); the replay
+ * sample indices out [B] of a batch drawn over a ring filled to `size` (tag 4, ctr (b, 0, 4, ctr));
+ * the target-smoothing draws eps [B][2], rounded to f32 as the kernels do before policy_noise and
+ * the clamp (tag 5, ctr (row, 0, 5, ctr)). */
+void orc_vec_noise(const orc_params_t* p, int64_t n, uint32_t step, double* z);
+void orc_sample_indices(const orc_params_t* p, int64_t B, int64_t size, uint32_t ctr,
+                        int64_t* out);
+void orc_smoothing_noise(const orc_params_t* p, int64_t B, uint32_t ctr, float* eps);
 
 /* Exact nearest-demo index (per index cell of width 1/ORC_DEMO_RES, the candidates that can be
  * nearest to any query in the cell; built from the 1 x 1 dynamics cells' lists):

@@ -90,6 +90,11 @@ def lib():
                                                C.c_int64, _dp, _dp, _dp, _dp, _u32p, _i32p, _i32p,
                                                _i32p, _dp, _dp, _dp, _fp, C.c_int64, C.c_int64,
                                                C.c_int64, _i64p, _i32p]
+        L.orc_vec_agent_step_batch_out.argtypes = L.orc_vec_agent_step_batch.argtypes + [_i32p, _dp]
+        L.orc_vec_noise.argtypes = [C.POINTER(Params), C.c_int64, C.c_uint32, _dp]
+        L.orc_sample_indices.argtypes = [C.POINTER(Params), C.c_int64, C.c_int64, C.c_uint32,
+                                         _i64p]
+        L.orc_smoothing_noise.argtypes = [C.POINTER(Params), C.c_int64, C.c_uint32, _fp]
         L.orc_demo_index_res.restype = C.c_int32
         L.orc_demo_index_build.restype = C.c_int64
         L.orc_demo_index_build.argtypes = [_dp, C.c_int64, _i64p, _i32p, C.c_int64]
@@ -285,14 +290,70 @@ class VecAgentState:
             ptr(row, _fp), C.byref(r), None if rs is None else ptr(rs, _dp))
         return flags, ns, row, r.value
 
-    def step_batch(self, p, speed, angle, demo, action, rows, base, env0=0):
+
+    def step_batch(self, p, speed, angle, demo, action, rows, base, lo=0, hi=None, index=None):
+        """One tick of envs [lo, hi) of the mirror (default: all) against one demo set, OpenMP
+        over the envs: orc_vec_agent_tick for each, env `e` ticking as global env `e` (its own
+        reset draw), so a caller with several demo groups makes one call per group. `action` is
+        the whole mirror's [n][2]; env e's replay row lands in rows[(base + e) % len(rows)].
+        `index` (a DemoIndexCPU of `demo`, optional) takes the demo minimum through the exact
+        index instead of brute force: the same f64 value. Returns (next_state [hi - lo][2], flags
+        [hi - lo] int32, reward [hi - lo] f64)."""
+        hi = self.n if hi is None else hi
+        assert 0 <= lo <= hi <= self.n
+        k = hi - lo
         demo = np.ascontiguousarray(demo, np.float64).reshape(-1, 2)
-        ns = np.zeros((self.n, 2))
-        lib().orc_vec_agent_step_batch(
+        speed = np.ascontiguousarray(speed, np.float32)
+        angle = np.ascontiguousarray(angle, np.float32)
+        a = np.ascontiguousarray(np.asarray(action, np.float64)[lo:hi])
+        assert a.shape == (k, 2)
+        assert rows.dtype == np.float32 and rows.ndim == 2 and rows.shape[1] == 8
+        ns = np.zeros((k, 2)); flags = np.zeros(k, np.int32); reward = np.zeros(k)
+        if k == 0:
+            return ns, flags, reward
+        if index is not None:
+            assert index.demo.shape == demo.shape
+        V = lambda arr, t: arr[lo:].ctypes.data_as(t)  # noqa: E731
+        lib().orc_vec_agent_step_batch_out(
             C.byref(p), ptr(speed, _fp), ptr(angle, _fp), ptr(demo, _dp) if len(demo) else None,
-            len(demo), self.n, ptr(self.state, _dp), ptr(self.goal, _dp), ptr(self.region, _dp),
-            ptr(self.hist, _dp), ptr(self.meta, _u32p), ptr(self.plan_index, _i32p),
-            ptr(self.path_length, _i32p), ptr(self.episodes, _i32p), ptr(self.noise_scale, _dp),
-            ptr(np.ascontiguousarray(action, np.float64), _dp), ptr(ns, _dp), ptr(rows, _fp),
-            rows.shape[0], base, env0)
-        return ns
+            len(demo), k, V(self.state, _dp), V(self.goal, _dp), V(self.region, _dp),
+            V(self.hist, _dp), V(self.meta, _u32p), V(self.plan_index, _i32p),
+            V(self.path_length, _i32p), V(self.episodes, _i32p), V(self.noise_scale, _dp),
+            ptr(a, _dp), ptr(ns, _dp), ptr(rows, _fp), rows.shape[0],
+            (base + lo) % rows.shape[0], lo,
+            None if index is None else ptr(index.start, _i64p),
+            None if index is None else ptr(index.cand, _i32p), ptr(flags, _i32p),
+            ptr(reward, _dp))
+        return ns, flags, reward
+
+
+# ---- the product path's in-kernel Philox streams (include/navenv.h:39-41), batched ----
+def vec_noise(p, n, step):
+    """Exploration noise z [n][2] f64 of vector step `step`: vec_noise_one for every env."""
+    z = np.zeros((n, 2))
+    lib().orc_vec_noise(C.byref(p), n, int(step) & 0xFFFFFFFF, ptr(z, _dp))
+    return z
+
+
+def sample_indices(p, B, size, ctr):
+    """Replay rows [B] int64 of one learner batch drawn over a ring filled to `size`."""
+    out = np.zeros(B, np.int64)
+    lib().orc_sample_indices(C.byref(p), B, int(size), int(ctr) & 0xFFFFFFFF, ptr(out, _i64p))
+    return out
+
+
+def smoothing_noise(p, B, ctr):
+    """Target-policy smoothing draws eps [B][2] f32 (before policy_noise and the clamp)."""
+    eps = np.zeros((B, 2), np.float32)
+    lib().orc_smoothing_noise(C.byref(p), B, int(ctr) & 0xFFFFFFFF, ptr(eps, _fp))
+    return eps
+
+
+def learner_counters(update_counter):
+    """The Philox counters TD3 epoch `update_counter` draws with (nav/td3.py passes update_counter
+    to both row launches; nav_td3_critic_rows and nav_td3_actor_rows derive, in uint32,
+    mlp_kernels.hip:2535-2536, 2572): the critic's batch 2 c, the actor's batch 2 c + 1, the
+    smoothing noise c."""
+    c = int(update_counter) & 0xFFFFFFFF
+    return {"critic_sample": (2 * c) & 0xFFFFFFFF, "actor_sample": (2 * c + 1) & 0xFFFFFFFF,
+            "smoothing": c}

@@ -1,7 +1,7 @@
 """GPU checks at the bench configuration (BASELINE config 3: 65 536 envs in 64 groups of 1 024,
-2x256 actor/critic, TD3 batch 32 768): the fused tick of a random subset of envs spread over every
-group against the oracle's restated tick (robot.py:645-675, 727-762, environment.py:98-137) on the
-same inputs, and size-independent invariants of the whole state and of the learner after it."""
+2x256 actor/critic, TD3 batch 32 768): the trainer's fused act + tick launch of every env against
+the oracle's restated tick (robot.py:645-675, 727-762, environment.py:98-137) on the same inputs,
+and size-independent invariants of the whole state and of the learner after it."""
 import numpy as np
 import pytest
 import torch
@@ -25,46 +25,95 @@ def trainer():
     return tr
 
 
+_MIRROR = ("state", "goal", "region", "meta", "plan_index", "path_length", "episodes",
+           "noise_scale")
+
+
+def _sync_oracle(env, ost):
+    for k in _MIRROR:
+        getattr(ost, k)[:] = getattr(env, k).cpu().numpy()
+    ost.hist[:] = env.hist.cpu().numpy().transpose(1, 0, 2)
+
+
 def test_bench_config_tick_subset_vs_oracle(trainer, orc):
-    from oracle import oracle as O
+    """nav_act_tick, the trainer's collect launch, for 3 consecutive ticks of all 65 536 envs
+    against the oracle's tick (VecAgentState.step_batch, one call per demo group, brute-force
+    demo minimum) on the device's own actions, the oracle re-synced from the device state before
+    each tick: next_state and state within 1e-11, replay rows at rtol / atol 1e-5, flags, meta,
+    counters and noise_scale equal, block_stats' reward within 1e-5 of the block's magnitude sum
+    and its counts exact. The learner is not called. Before the first tick the state is edited
+    from the host so that every branch is taken: envs e % 8 == 0 stand two ticks before their
+    plan's end, envs e % 8 == 1 on their goal."""
     tr, env = trainer, trainer.env
     n = tr.n
     fields = env.field.cpu().numpy()
     speed, angle = np.ascontiguousarray(fields[..., 0]), np.ascontiguousarray(fields[..., 1])
-    ost = O.VecAgentState(n)
-    ost.state[:] = env.state.cpu().numpy()
-    ost.goal[:] = env.goal.cpu().numpy()
-    ost.region[:] = env.region.cpu().numpy()
-    ost.hist[:] = env.hist.cpu().numpy().transpose(1, 0, 2)
-    ost.meta[:] = env.meta.cpu().numpy().astype(np.uint32)
-    ost.plan_index[:] = env.plan_index.cpu().numpy()
-    ost.path_length[:] = env.path_length.cpu().numpy()
-    ost.episodes[:] = env.episodes.cpu().numpy()
-    ost.noise_scale[:] = env.noise_scale.cpu().numpy()
     pts = env.demo_xy.cpu().numpy()
     off = env.demo_off.cpu().numpy()
-    epg = n // (len(off) - 1)
-    p = O.default_params(tr.seed)
-    tr.act()
-    a = tr.action.cpu().numpy()
-    assert np.isfinite(a).all() and np.abs(a).max() <= 5.0
-    base = tr.replay.position
-    env.agent_step(tr.action, tr.replay)
-    torch.cuda.synchronize()
-    rows = tr.replay.rows.cpu().numpy()
-    nxt = env.next_state.cpu().numpy()
-    st = env.state.cpu().numpy()
-    rng = np.random.default_rng(5)
-    idx = np.concatenate([g * epg + rng.choice(epg, 2, replace=False)
-                          for g in range(len(off) - 1)])
-    for e in idx:
-        grp = e // epg
-        fl, ns, row, r = ost.tick(p, speed, angle, pts[off[grp]:off[grp + 1]], int(e), a[e])
-        assert np.max(np.abs(ns - nxt[e])) < 1e-11, e
-        assert np.allclose(row, rows[(base + e) % tr.replay.capacity], rtol=1e-5, atol=1e-5), e
-        assert np.max(np.abs(ost.state[e] - st[e])) < 1e-11, e
-    for k in ("plan_index", "path_length", "episodes"):
-        assert np.array_equal(getattr(env, k)[idx].cpu().numpy(), getattr(ost, k)[idx]), k
+    G = len(off) - 1
+    epg = n // G
+    assert G == 64 and epg == env.envs_per_group
+    p = orc.default_params(tr.seed)
+    e = torch.arange(n, device=DEV)
+    env.plan_index[e % 8 == 0] = env.path_length[e % 8 == 0] - 2
+    env.state[e % 8 == 1] = env.goal[e % 8 == 1]
+    tr.sync_collect()
+    ost = orc.VecAgentState(n)
+    cap = tr.replay.capacity
+    rows_o = np.zeros((cap, 8), np.float32)
+    seen = dict(done=0, goal=0, stuck=0, ended=0, demo_term=0)
+    for t in range(3):
+        _sync_oracle(env, ost)
+        demo_flag = (ost.meta & 4) != 0
+        base = tr.replay.position
+        reward = torch.full((n,), float("nan"), dtype=torch.float64, device=DEV)
+        assert tr.fuse_tick
+        env.act_tick(tr.td3.actor_network, tr.steps, tr.replay, action_out=tr.action,
+                     reward_out=reward)
+        tr.steps += 1
+        torch.cuda.synchronize()
+        assert tr.replay.position == (base + n) % cap
+        a = tr.action.cpu().numpy()
+        assert np.isfinite(a).all() and np.abs(a).max() <= 5.0
+        ns_o = np.zeros((n, 2)); fl_o = np.zeros(n, np.int32); r_o = np.zeros(n)
+        for g in range(G):
+            lo, hi = g * epg, (g + 1) * epg
+            ns_o[lo:hi], fl_o[lo:hi], r_o[lo:hi] = ost.step_batch(
+                p, speed, angle, pts[off[g]:off[g + 1]], a, rows_o, base, lo, hi)
+        d_ns = np.abs(env.next_state.cpu().numpy() - ns_o).max()
+        d_st = np.abs(env.state.cpu().numpy() - ost.state).max()
+        print(f"tick {t}: max |next_state diff| {d_ns:.2e}, max |state diff| {d_st:.2e}")
+        assert d_ns < 1e-11 and d_st < 1e-11, t
+        slots = (base + np.arange(n)) % cap
+        got = tr.replay.rows.cpu().numpy()[slots]
+        bad = ~np.isclose(rows_o[slots], got, rtol=1e-5, atol=1e-5).all(1)
+        assert not bad.any(), (t, np.nonzero(bad)[0][:8])
+        fl_dev = env.flags.cpu().numpy().astype(np.int32)
+        assert np.array_equal(fl_dev & 15, fl_o & 15), t
+        assert np.array_equal(env.meta.cpu().numpy().astype(np.uint32), ost.meta), t
+        for k in ("plan_index", "path_length", "episodes", "noise_scale"):
+            assert np.array_equal(getattr(env, k).cpu().numpy(), getattr(ost, k)), (t, k)
+        # the launch's per-64-env reductions: the pushed reward (demo term included), the done /
+        # goal / stuck / ended counts
+        bs = env.block_stats.cpu().numpy().astype(np.float64)
+        rows64 = lambda v: np.asarray(v, np.float64).reshape(-1, 64).sum(1)  # noqa: E731
+        mag = rows64(np.abs(r_o))
+        assert np.all(np.abs(bs[:, 0] - rows64(r_o)) <= 1e-5 * np.maximum(1.0, mag)), t
+        for c in range(4):
+            assert np.array_equal(bs[:, 1 + c], rows64((fl_o >> c) & 1)), (t, c)
+        assert (bs[:, 5:] == 0).all()
+        # the device took the demo term exactly where the oracle did, and reported its reward
+        took = demo_flag & ((fl_o & 2) == 0)
+        assert np.array_equal((fl_dev & 16) != 0, took), t
+        r_dev = reward.cpu().numpy()
+        tol = 1e-9 * np.maximum(1.0, np.abs(r_o[took]))  # test_agent_step_replays_reference_trace's
+        assert np.all(np.abs(r_dev[took] - r_o[took]) <= tol), t
+        for bit, key in enumerate(("done", "goal", "stuck", "ended")):
+            seen[key] += int(((fl_o >> bit) & 1).sum())
+        seen["demo_term"] += int(took.sum())
+    print(seen)
+    for key in ("done", "goal", "ended", "demo_term"):
+        assert seen[key] >= 100, seen
 
 
 def test_bench_config_invariants(trainer):
@@ -72,9 +121,18 @@ def test_bench_config_invariants(trainer):
     tr.step()
     torch.cuda.synchronize()
     s = env.state.cpu().numpy()
-    assert np.isfinite(s).all() and s.min() >= 0.0 and s.max() <= 100.0 - 1.0001
     plan, path = env.plan_index.cpu().numpy(), env.path_length.cpu().numpy()
     assert (plan >= 1).all() and (plan < path).all()  # an episode ends at plan == path - 1
+    # a state that Environment.step produced lies inside the dynamics clip; an env whose episode
+    # just ended (plan_index 1) stands on its reset draw instead, anywhere in its init region
+    # (environment.py:135-137; a region reaches the world's edge at 100). The tick test above
+    # ends thousands of episodes on this fixture, so both kinds are here.
+    assert np.isfinite(s).all() and s.min() >= 0.0
+    fresh = plan == 1
+    reg = env.region.cpu().numpy()
+    assert (s[~fresh] <= 100.0 - 1.0001).all()
+    assert ((s[fresh] >= reg[fresh][:, [0, 2]]) & (s[fresh] <= reg[fresh][:, [1, 3]])).all()
+    assert reg.min() >= 0.0 and reg.max() <= 100.0
     assert (env.episodes.cpu().numpy() >= 0).all()
     ns = env.noise_scale.cpu().numpy()
     assert np.isfinite(ns).all() and (ns > 0).all()

@@ -739,19 +739,12 @@ def test_split_gemm_per_row_accuracy_rows_spanning_binades(nav, M):
         err[live].max(), err[live].median(), err[live & (s > 12)].max()))
 
 
-@pytest.mark.parametrize("d_in,d_out,hidden,nh", [(2, 2, 200, 3), (4, 1, 200, 3), (2, 2, 256, 2),
-                                                  (4, 1, 256, 2), (4, 1, 192, 2)])
-@pytest.mark.parametrize("M", [4097, 16421])
-def test_split_gemm_f32_accuracy_vs_fp64(nav, d_in, d_out, hidden, nh, M):
-    """nav_mlp_forward and the row backward (nav_mlp_backward: dz rows and dx) against an fp64
-    reference of the same f32 weights and inputs: max |err| / max |ref| <= 2e-6 for every output,
-    saved activation, dz row and dx. fp32 itself sits at ~1e-7 here; the three-plane bf16 split
-    measured 3-4e-7, the scaled two-plane fp16 split (22 significant bits) 3-7e-7 in the probe, a
-    two-plane bf16 split (a 16-bit-mantissa GEMM, narrower than fp32) 6-8e-6 — the rtol 1e-4 tests
-    above pass all three, this one not the last. The row
-    backward's reference uses the kernel's own ReLU bits (a kink within rounding of 0 may take the
-    other branch in fp64; the bits are checked against the fp64 signs outside that band). Weight
-    gradients (cross-row sums) are held to 1e-5 of their scale."""
+def split_gemm_row_errors(d_in, d_out, hidden, nh, M):
+    """The launches and the fp64 reference of test_split_gemm_f32_accuracy_vs_fp64 at M rows.
+    Returns (rows, dW): rows[name] = (|err| per row [M] (the row's worst entry), max |ref|) for
+    the output, every saved activation h_l, every dz_l and dx; dW[name] = max |err| / max |ref|
+    of every hidden x hidden weight gradient. Asserts on the way that the forward's ReLU bits
+    equal the fp64 signs outside the rounding band."""
     from nav._lib import descs, lib, parr, ptr, stream_handle
     from nav.mlp import forward
     net, layers = make_net(d_in, d_out, hidden, nh, 17)
@@ -779,14 +772,14 @@ def test_split_gemm_f32_accuracy_vs_fp64(nav, d_in, d_out, hidden, nh, M):
     L.nav_grad_reduce(C.byref(net.desc()), ptr(hs), splits, ptr(eslab), nblk, ptr(grad), s)
     torch.cuda.synchronize()
 
-    def rel(a, ref):
-        return float((a.double() - ref).abs().max() / ref.abs().max())
+    def per_row(a, ref):
+        return (a.double() - ref).abs().reshape(M, -1).amax(1), float(ref.abs().max())
 
-    errs = {}
+    rows, dW = {}, {}
     ref, zs = _f64_forward(layers, x)
-    errs["out"] = rel(out.cpu(), ref)
+    rows["out"] = per_row(out.cpu(), ref)
     for l in range(nh):
-        errs[f"h{l}"] = rel(acts[l].cpu()[:, :hidden], torch.relu(zs[l]))
+        rows[f"h{l}"] = per_row(acts[l].cpu()[:, :hidden], torch.relu(zs[l]))
     # fp64 row backward with the kernel's ReLU bits
     bits = relu_bits(masks, nh, net.hp, hidden, M)
     hs64 = [x.double()] + [torch.relu(z) for z in zs]
@@ -799,16 +792,36 @@ def test_split_gemm_f32_accuracy_vs_fp64(nav, d_in, d_out, hidden, nh, M):
     gW = {}
     for l in range(nh - 1, -1, -1):
         gz = gz * bits[l].double()                              # dL/dz_l
-        errs[f"dz{l}"] = rel(dz[l].cpu()[:, :hidden], gz)
+        rows[f"dz{l}"] = per_row(dz[l].cpu()[:, :hidden], gz)
         gW[l] = gz.t() @ hs64[l]
         gz = gz @ layers[l][0].double()                         # dL/dh_{l-1} (l = 0: dL/dx)
-    errs["dx"] = rel(dx.cpu(), gz)
+    rows["dx"] = per_row(dx.cpu(), gz)
     from nav.mlp import layer_offsets
     offs, _ = layer_offsets(d_in, d_out, net.hp, nh)
     gflat = grad.cpu()
     for l in range(1, nh):
         w_off, _, fo, fi = offs[l]
-        errs[f"dW{l}"] = rel(gflat[w_off:w_off + fo * fi].view(fo, fi)[:hidden, :hidden], gW[l])
+        got = gflat[w_off:w_off + fo * fi].view(fo, fi)[:hidden, :hidden]
+        dW[f"dW{l}"] = float((got.double() - gW[l]).abs().max() / gW[l].abs().max())
+    return rows, dW
+
+
+@pytest.mark.parametrize("d_in,d_out,hidden,nh", [(2, 2, 200, 3), (4, 1, 200, 3), (2, 2, 256, 2),
+                                                  (4, 1, 256, 2), (4, 1, 192, 2)])
+@pytest.mark.parametrize("M", [4097, 16421])
+def test_split_gemm_f32_accuracy_vs_fp64(nav, d_in, d_out, hidden, nh, M):
+    """nav_mlp_forward and the row backward (nav_mlp_backward: dz rows and dx) against an fp64
+    reference of the same f32 weights and inputs: max |err| / max |ref| <= 2e-6 for every output,
+    saved activation, dz row and dx. fp32 itself sits at ~1e-7 here; the three-plane bf16 split
+    measured 3-4e-7, the scaled two-plane fp16 split (22 significant bits) 3-7e-7 in the probe, a
+    two-plane bf16 split (a 16-bit-mantissa GEMM, narrower than fp32) 6-8e-6 — the rtol 1e-4 tests
+    above pass all three, this one not the last. The row
+    backward's reference uses the kernel's own ReLU bits (a kink within rounding of 0 may take the
+    other branch in fp64; the bits are checked against the fp64 signs outside that band). Weight
+    gradients (cross-row sums) are held to 1e-5 of their scale."""
+    rows, dW = split_gemm_row_errors(d_in, d_out, hidden, nh, M)
+    errs = {k: float(e.max()) / scale for k, (e, scale) in rows.items()}
+    errs.update(dW)
     print({k: f"{v:.2e}" for k, v in errs.items()})
     for k, v in errs.items():
         assert v <= (1e-5 if k.startswith("dW") else 2e-6), (k, v)
@@ -975,7 +988,8 @@ def test_packed_images_exact_after_pack_adam_polyak(nav, hidden, nh):
     """The fp16 B-operand images that the hidden GEMMs read follow the weights after every writer
     (the exact two-plane decomposition of _assert_images_exact): nav_mlp_pack, nav_adam,
     nav_polyak, and the product path's fused reduce + Adam + soft updates
-    (nav_grad_reduce_adam_polyak), targets included."""
+    (nav_grad_reduce_adam_polyak), targets included; and on d_out = 1 critics, whose top backward
+    image carries Wo, after nav_adam and after the critics' fused nav_grad_reduce_adam."""
     from nav._lib import descs, lib, parr, ptr, stream_handle
     L = lib()
     s = stream_handle()
@@ -1008,6 +1022,30 @@ def test_packed_images_exact_after_pack_adam_polyak(nav, hidden, nh):
     for t, tag in ((net, "reduce_adam"), (tgt, "own_target"), (ctgt[0], "pair0"),
                    (ctgt[1], "pair1")):
         _assert_images_exact(t, tag)
+    # d_out = 1: the top layer's backward image is Wt[k][n] = Wo[k] W[k][n], so it also follows
+    # every Adam step's new Wo. nav_adam, then the critics' product path: both twins in one
+    # nav_grad_reduce_adam launch (every entry of the gradient non-zero, Wo's included).
+    opt1 = _Adam(crit[0], 1e-3)
+    opt1.step((torch.randn(crit[0].count, generator=g) * 1e-2).to(DEV))
+    torch.cuda.synchronize()
+    _assert_images_exact(crit[0], "adam_d_out_1")
+    ec = L.nav_mlp_edge_count(4, 1, hp, nh)
+    hs2 = [hs.clone(), (hs * -0.5).contiguous()]
+    es2 = [torch.randn(nblk, ec, generator=g).to(DEV) * 1e-2 for _ in range(2)]
+    cc = crit[0].count
+    m2 = [torch.randn(cc, device=DEV) * 1e-3 for _ in range(2)]
+    v2 = [torch.rand(cc, device=DEV) * 1e-4 for _ in range(2)]
+    g2 = [torch.zeros(cc, device=DEV) for _ in range(2)]
+    wo_off = crit[0].offsets[nh][0]
+    wo_before = [c.params[wo_off:wo_off + hidden].clone() for c in crit]
+    assert L.nav_grad_reduce_adam(
+        descs(*crit), 2, parr(*hs2), splits, parr(*es2), nblk, parr(*g2), parr(*m2), parr(*v2),
+        0.9, 0.999, 1e-8, (C.c_float * 2)(1e-2, 2e-2), (C.c_float * 2)(0.5, 0.25), s) == 0
+    torch.cuda.synchronize()
+    for k in range(2):
+        moved = crit[k].params[wo_off:wo_off + hidden] != wo_before[k]
+        assert moved.float().mean() > 0.9, k  # Wo itself stepped: the image must follow it
+        _assert_images_exact(crit[k], f"reduce_adam_d_out_1[{k}]")
 
 
 def _flat_to_tensors(net, flat):
