@@ -333,6 +333,45 @@ int nav_test_rollout(const nav_params* p, const nav_mlp* actor, const nav_env_so
                      const float* field, const double* start, uint32_t episode,
                      int32_t max_steps, const nav_test_out* out, void* stream);
 
+/* ---- Populations: P members with their own actor, constants and replay ring in ONE launch ----
+ * env->n = n_members * envs_per_member; member m owns the consecutive envs [m * envs_per_member,
+ * (m + 1) * envs_per_member). `params`, `actors` and `replays` are host arrays [n_members].
+ * Every entry point below checks on the host, before any HIP call (NAV_EINVAL): n_members in
+ * 1 .. 256; envs_per_member a multiple of 64 (a workgroup sees one member) and, when a demo set
+ * is given, of envs_per_group; the actors' d_in / d_out / hidden / hidden_pad / n_hidden equal;
+ * the members' world_size, init_region_size, seed_lo / seed_hi and max_goal_draws equal (they
+ * key the Philox streams and the init); ring capacities equal and >= envs_per_member; no null
+ * pointer. Every other field of nav_params may differ per member.
+ * `table` is device memory of nav_pop_table_bytes(n_members) bytes that nav_pop_table_build
+ * fills on the stream from the same arrays (replays nullable: a table for test rollouts only):
+ * the kernels read member m's actor descriptor, constants and ring pointer from it. Build it
+ * once per population, not per step, and again only when a descriptor's pointers, a constant
+ * or a ring changes (updating the weights in place needs no rebuild). The launch entry points
+ * take the host arrays for the check and the launch shape only; a table built from other
+ * arrays is the caller's error. */
+int64_t nav_pop_table_bytes(int32_t n_members);
+int nav_pop_table_build(const nav_params* params, const nav_mlp* actors,
+                        const nav_replay* replays, int32_t n_members, int32_t envs_per_member,
+                        void* table, void* stream);
+/* nav_act_tick for every member in one launch: member m's rows run actors[m] and params[m] and
+ * push to ring m; env e of member m writes slot (replay_base + e - m * envs_per_member) %
+ * capacity of ring m (one replay_base for all). Exploration noise stays keyed by the global env
+ * index and the common seed, demo groups by the global env index. Member m's envs end exactly
+ * as after nav_act_tick over the whole env set with actors[m] and params[m], bit for bit. */
+int nav_act_tick_pop(const nav_params* params, const nav_mlp* actors, const nav_replay* replays,
+                     int32_t n_members, int32_t envs_per_member, const void* table,
+                     const nav_env_soa* env, const float* field, const double* noise_z,
+                     uint32_t step, int32_t mode, int64_t replay_base, const nav_step_out* out,
+                     const double* demo_xy, const int64_t* demo_off, int32_t envs_per_group,
+                     const int64_t* cell_start, const int32_t* cand, double* action_out,
+                     double* reward_out, void* stream);
+/* nav_test_rollout for every member in one launch: member m's envs run actors[m] with
+ * params[m]'s max_action and goal_threshold; start draws stay keyed by the global env index. */
+int nav_test_rollout_pop(const nav_params* params, const nav_mlp* actors, int32_t n_members,
+                         int32_t envs_per_member, const void* table, const nav_env_soa* env,
+                         const float* field, const double* start, uint32_t episode,
+                         int32_t max_steps, const nav_test_out* out, void* stream);
+
 /* Generic forward of up to 2 networks sharing one input (twin critics), rows [M]:
  * x = in[m*ld_in + in_col + 0..d_in) (f32). out_mode 0: out[m*ld_out + out_col + j] = y;
  * out_mode 1 (target policy smoothing, robot.py:336-339): out = clamp(y + clamp(policy_noise*eps,

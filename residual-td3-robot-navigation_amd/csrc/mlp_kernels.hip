@@ -565,8 +565,20 @@ NAV_DEV const float* img_bwd(const MlpDev& net, int L) {
 }
 
 enum { IN_F32 = 0, IN_BASELINE = 1 };
-enum { OUT_F32 = 0, OUT_TARGET = 1, OUT_ACT = 2, OUT_LOSS = 3, OUT_TICK = 4 };
+enum { OUT_F32 = 0, OUT_TARGET = 1, OUT_ACT = 2, OUT_LOSS = 3, OUT_TICK = 4, OUT_TICK_POP = 5 };
 
+// One member of a population (nav_act_tick_pop / nav_test_rollout_pop): its actor, its constants
+// and its replay ring. The device-resident table [n_members] is written once per population
+// (nav_pop_table_build); a workgroup's rows all belong to one member, so its entry is read
+// through a block-uniform pointer.
+struct PopMember {
+    MlpDev net;
+    nav_params p;
+    float4* rows;      // the member's ring (null in a table built without rings: test rollouts)
+    int64_t base_off;  // (-m * envs_per_member) mod capacity: (replay_base + base_off) % capacity
+                       // + global env index is the member-local slot, so push_row's and the demo
+                       // pass's (base + e) % cap hold as they are
+};
 
 struct FwdArgs {
     MlpDev net[2];
@@ -610,6 +622,11 @@ struct FwdArgs {
     nav_step_out sout;
     DemoIdx demo;
     double* reward_out;
+    // OUT_TICK_POP: the member table and the workgroups per member (net[0], rows and
+    // max_action_d above are then unused and p carries the members' common seed only; cap is
+    // the members' common capacity, base the common replay_base % cap)
+    const PopMember* pop;
+    int32_t pop_blocks;
 };
 
 // Output-layer partial sums: [d_out <= 2][4 waves][TM rows] (red_floats per block).
@@ -1081,7 +1098,11 @@ __global__ __launch_bounds__(kBlock, 1) void k_mlp_fwd(FwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int hp = NT * 32, SS = hp + 4, TM = RT * 32;
     const int tid = threadIdx.x;
-    const MlpDev& net = a.net[blockIdx.y];
+    // OUT_TICK_POP: the tick of OUT_TICK with the workgroup's member's actor, constants and ring
+    constexpr bool POP = OUT_MODE == OUT_TICK_POP, TICK = OUT_MODE == OUT_TICK || POP;
+    const PopMember* pm = nullptr;
+    if constexpr (POP) pm = a.pop + blockIdx.x / (unsigned)a.pop_blocks;
+    const MlpDev& net = POP ? pm->net : a.net[blockIdx.y];
     float* act_save = a.acts[blockIdx.y];
     uint16_t* masks = a.masks[blockIdx.y];
     const int64_t M = a.M;
@@ -1095,6 +1116,15 @@ __global__ __launch_bounds__(kBlock, 1) void k_mlp_fwd(FwdArgs a) {
     // layer 0's per-lane weights and bias: issued first, in flight under the input rows' loads
     const L0Pre l0 = load_l0<NT>(net);
     if constexpr (OUT_MODE == OUT_TICK) NAV_CLOCK(2, 0);
+    // the member's ring, its base and its action bound: block-uniform loads ahead of the pass
+    float4* prows = nullptr;
+    int64_t pbase = 0;
+    double pmax = 0.0;
+    if constexpr (POP) {
+        prows = pm->rows;
+        pbase = (a.base + pm->base_off) % a.cap;
+        pmax = pm->p.max_action;
+    }
 
     // ---- input rows -> xin
     if (tid < TM) {
@@ -1122,7 +1152,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_mlp_fwd(FwdArgs a) {
     TickIn tin{};
     double nsc = 0.0;
     double2 zz = make_double2(0.0, 0.0);
-    if constexpr (OUT_MODE == OUT_TICK) {
+    if constexpr (TICK) {
         const int64_t r = row0 + tid;
         if (tid < TM && r < M) {
             tin = tick_load(a.env, a.field, r);
@@ -1141,7 +1171,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_mlp_fwd(FwdArgs a) {
     float* red = xin + TM * 4;  // [2][PARTS][TM]
     f32x16 top[RT][2];
     fwd_net<NT, RT, kPfWide, IN_MODE == IN_BASELINE ? 2 : 0>(net, act, stage, xin, red, masks, n_rt, act_save, a.save_mask, row0, M, rt0, top,
-                    OUT_MODE == OUT_TICK ? NAV_TICK_MK : -64, &l0);
+                    TICK ? NAV_TICK_MK : -64, &l0);
     const int rloc = tid % TM;
     const int j = tid / TM;
     const int64_t r = row0 + rloc;
@@ -1159,7 +1189,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_mlp_fwd(FwdArgs a) {
                               a.eslab[q] ? a.eslab[q] + (int64_t)blockIdx.x * a.ecount : nullptr);
         return;
     }
-    if constexpr (OUT_MODE == OUT_TICK) {
+    if constexpr (TICK) {
         // robot.py:556-567 as OUT_ACT, the action parked in LDS (the input rows are done with),
         // then the tick of env row0 + t by thread t < TM: nav_agent_step's device code
         // the row's thread forms both action components (the same expressions per component as
@@ -1174,24 +1204,45 @@ __global__ __launch_bounds__(kBlock, 1) void k_mlp_fwd(FwdArgs a) {
                 const float y = out_y<RT>(net, red, tid, jj);
                 const double sj = jj == 0 ? tin.s.x : tin.s.y, gj = jj == 0 ? tin.g.x : tin.g.y;
                 double c = (sj - gj) + (double)y;
-                if (a.act_mode == 0) c = c + (nsc * a.max_action_d) * (jj == 0 ? zz.x : zz.y);
-                v[jj] = clipd(c, -a.max_action_d, a.max_action_d);
+                if constexpr (POP) {
+                    if (a.act_mode == 0) c = c + (nsc * pmax) * (jj == 0 ? zz.x : zz.y);
+                    v[jj] = clipd(c, -pmax, pmax);
+                } else {
+                    if (a.act_mode == 0)
+                        c = c + (nsc * a.max_action_d) * (jj == 0 ? zz.x : zz.y);
+                    v[jj] = clipd(c, -a.max_action_d, a.max_action_d);
+                }
                 if (a.action_out) a.action_out[r * 2 + jj] = v[jj];
             }
             const double2 av = make_double2(v[0], v[1]);
-            st = a.demo.cand ? agent_tick_in<true>(a.p, a.env, r, tin, av, a.rows, a.cap, a.base,
-                                                   a.sout, true, pend)
-                             : agent_tick_in<false>(a.p, a.env, r, tin, av, a.rows, a.cap,
-                                                    a.base, a.sout, false, pend);
+            // (the plain tick's statements stand beside the member's, not merged with them
+            // through selects: merged, its scalar loads came out of the compiler elsewhere)
+            if constexpr (POP)
+                st = a.demo.cand ? agent_tick_in<true>(pm->p, a.env, r, tin, av, prows, a.cap,
+                                                       pbase, a.sout, true, pend)
+                                 : agent_tick_in<false>(pm->p, a.env, r, tin, av, prows, a.cap,
+                                                        pbase, a.sout, false, pend);
+            else
+                st = a.demo.cand ? agent_tick_in<true>(a.p, a.env, r, tin, av, a.rows, a.cap,
+                                                       a.base, a.sout, true, pend)
+                                 : agent_tick_in<false>(a.p, a.env, r, tin, av, a.rows, a.cap,
+                                                        a.base, a.sout, false, pend);
         }
         NAV_TRACE_MARK(NAV_TICK_MK + 7);
         if (a.demo.cand) {  // block-uniform: the demo pass of the block's envs, all threads
             // the LDS rows are done with (the actions live in xin)
             auto* scratch = reinterpret_cast<DemoScratch<TM, kBlock>*>(act);
-            const double rd = demo_pass<TM, kBlock>(a.p, a.demo, *scratch, pend, r,
-                                                    reinterpret_cast<float*>(a.rows), a.cap,
-                                                    a.base, a.reward_out);
-            if (pend.need) st.r = (float)rd;  // the final reward of a flagged env
+            if constexpr (POP) {
+                const double rd = demo_pass<TM, kBlock>(pm->p, a.demo, *scratch, pend, r,
+                                                        reinterpret_cast<float*>(prows), a.cap,
+                                                        pbase, a.reward_out);
+                if (pend.need) st.r = (float)rd;
+            } else {
+                const double rd = demo_pass<TM, kBlock>(a.p, a.demo, *scratch, pend, r,
+                                                        reinterpret_cast<float*>(a.rows), a.cap,
+                                                        a.base, a.reward_out);
+                if (pend.need) st.r = (float)rd;  // the final reward of a flagged env
+            }
         }
         NAV_TRACE_MARK(NAV_TICK_MK + 8);
         if (tid < TM && a.sout.block_stats && row0 + (tid & ~63) < M)
@@ -1251,6 +1302,10 @@ struct TestArgs {
     uint32_t seed_lo, seed_hi, episode;
     int32_t max_steps;
     nav_test_out out;
+    // k_test_rollout<.., POP>: the member table and the workgroups per member (net, max_action and
+    // goal_threshold above are then unused)
+    const PopMember* pop;
+    int32_t pop_blocks;
 };
 
 // bytes of the row kernels' LDS layout (lds_bytes) on the device side: the test rollout parks its
@@ -1268,12 +1323,21 @@ __host__ __device__ constexpr size_t lds_bytes_c(int hp, int tm) {
 // the two LDS flags alternate by step parity, so a step costs one barrier on top of fwd_net's
 // (step t's runners raise flag t & 1 while thread 0 clears the other, which was last read a
 // step ago and is next raised a step ahead, both behind fwd_net's barriers).
-template <int NT, int RT>
+// POP (nav_test_rollout_pop): the workgroup's member's actor, max_action and goal_threshold from
+// the member table; the start draw stays keyed by the global env index and the common seed.
+template <int NT, int RT, bool POP = false>
 __global__ __launch_bounds__(kBlock, 1) void k_test_rollout(TestArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int hp = NT * 32, SS = hp + 4, TM = RT * 32;
     const int tid = threadIdx.x;
-    const MlpDev& net = a.net;
+    const PopMember* pm = nullptr;
+    if constexpr (POP) pm = a.pop + blockIdx.x / (unsigned)a.pop_blocks;
+    const MlpDev& net = POP ? pm->net : a.net;
+    double pmax = 0.0, pthr = 0.0;  // block-uniform loads, once, outside the step loop
+    if constexpr (POP) {
+        pmax = pm->p.max_action;
+        pthr = pm->p.goal_threshold;
+    }
     const int64_t n = a.n, row0 = (int64_t)blockIdx.x * TM, r = row0 + tid;
     float* act = smem;
     float* xin = smem + TM * SS;   // [TM][4]
@@ -1327,7 +1391,8 @@ __global__ __launch_bounds__(kBlock, 1) void k_test_rollout(TestArgs a) {
             for (int jj = 0; jj < 2; ++jj) {
                 const float y = out_y<RT>(net, red, tid, jj);
                 const double sj = jj == 0 ? s.x : s.y, gj = jj == 0 ? g.x : g.y;
-                v[jj] = clipd((sj - gj) + (double)y, -a.max_action, a.max_action);
+                const double max_action = POP ? pmax : a.max_action;
+                v[jj] = clipd((sj - gj) + (double)y, -max_action, max_action);
             }
             // environment.py:122-127
             const double2 nx = dynamics_f(fv, s, make_double2(v[0], v[1]));
@@ -1335,7 +1400,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_test_rollout(TestArgs a) {
             // robot-learning.py:107, 113-114
             const double d = norm2(s.x - g.x, s.y - g.y);
             best = d < best ? d : best;
-            if (d <= a.goal_threshold) {
+            if (d <= (POP ? pthr : a.goal_threshold)) {
                 reached = 1;
                 steps = t;
                 run = false;
@@ -2073,13 +2138,15 @@ int row_tiles_for(int64_t M, bool tick) { return (!tick && M <= kSmallRows) ? 1 
 // their own objects (this file built with NAV_MLP_PART = NT, see the Makefile) so the heavy
 // template instantiations compile in parallel; the main object (NAV_MLP_PART = 0) dispatches to
 // them through nav_mlp_rows_<NT>(). Argument structs travel as const void* (same definitions).
-enum { FAM_FWD = 0, FAM_BWD = 1, FAM_CRITIC = 2, FAM_ACTOR = 3, FAM_TEST = 4 };
+enum { FAM_FWD = 0, FAM_BWD = 1, FAM_CRITIC = 2, FAM_ACTOR = 3, FAM_TEST = 4, FAM_TEST_POP = 5 };
 
 }  // namespace
 
 #define NAV_ROWS_DECL(NT_)                                                                   \
     int nav_mlp_rows_##NT_(int fam, int rt, int in_mode, int out_mode, const void* args,      \
-                           int n_nets, hipStream_t st);
+                           int n_nets, hipStream_t st);                                       \
+    int nav_mlp_rows_pop_##NT_(int fam, int rt, int in_mode, int out_mode, const void* args,  \
+                               int n_nets, hipStream_t st);
 NAV_ROWS_DECL(1) NAV_ROWS_DECL(2) NAV_ROWS_DECL(3) NAV_ROWS_DECL(4)
 NAV_ROWS_DECL(5) NAV_ROWS_DECL(6) NAV_ROWS_DECL(7) NAV_ROWS_DECL(8)
 #undef NAV_ROWS_DECL
@@ -2154,11 +2221,11 @@ void launch_actor_rows_k(const ActorRowsArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k, dim3(gx, 1u + wy), dim3(kBlock), lds, st, w);
 }
 
-template <int NT, int RT>
+template <int NT, int RT, bool POP>
 void launch_test_k(const TestArgs& a, hipStream_t st) {
     constexpr int TM = RT * 32;
     const size_t lds = lds_bytes_c(NT * 32, TM) + 2 * sizeof(int);  // + the two loop flags
-    auto k = k_test_rollout<NT, RT>;
+    auto k = k_test_rollout<NT, RT, POP>;
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
     hipLaunchKernelGGL(k, dim3((unsigned)((a.n + TM - 1) / TM)), dim3(kBlock), lds, st, a);
@@ -2167,6 +2234,24 @@ void launch_test_k(const TestArgs& a, hipStream_t st) {
 template <int RT>
 int rows_rt(int fam, int in_mode, int out_mode, const void* args, int n_nets, hipStream_t st) {
     constexpr int NT = NAV_MLP_PART;
+#ifdef NAV_MLP_POP
+    // The population instantiations live in objects of their own (mlp_pop<NT>.o): compiled beside
+    // them, the plain tick kernel came out with a few scalar loads scheduled elsewhere, and the
+    // bench's kernels are to stay exactly as the compiler made them (tools/isa_diff.py).
+    if (fam == FAM_FWD && in_mode == IN_BASELINE && out_mode == OUT_TICK_POP) {
+        if constexpr (RT >= 2) {
+            launch_fwd_k<NT, RT, IN_BASELINE, OUT_TICK_POP>(*static_cast<const FwdArgs*>(args),
+                                                            n_nets, st);
+            return 0;
+        }
+        return NAV_EINVAL;
+    }
+    if (fam == FAM_TEST_POP) {
+        launch_test_k<NT, RT, true>(*static_cast<const TestArgs*>(args), st);
+        return 0;
+    }
+    return NAV_EINVAL;
+#else
     switch (fam) {
         case FAM_FWD: {
             const FwdArgs& a = *static_cast<const FwdArgs*>(args);
@@ -2194,23 +2279,31 @@ int rows_rt(int fam, int in_mode, int out_mode, const void* args, int n_nets, hi
         case FAM_ACTOR:
             launch_actor_rows_k<NT, RT>(*static_cast<const ActorRowsArgs*>(args), st);
             return 0;
-        case FAM_TEST: launch_test_k<NT, RT>(*static_cast<const TestArgs*>(args), st); return 0;
+        case FAM_TEST:
+            launch_test_k<NT, RT, false>(*static_cast<const TestArgs*>(args), st);
+            return 0;
         default: return NAV_EINVAL;
     }
+#endif
 }
 
 }  // namespace
 
 #define NAV_CAT2(a, b) a##b
 #define NAV_CAT(a, b) NAV_CAT2(a, b)
-int NAV_CAT(nav_mlp_rows_, NAV_MLP_PART)(int fam, int rt, int in_mode, int out_mode,
-                                           const void* args, int n_nets, hipStream_t st) {
+#ifdef NAV_MLP_POP
+#define NAV_ROWS_NAME NAV_CAT(nav_mlp_rows_pop_, NAV_MLP_PART)
+#else
+#define NAV_ROWS_NAME NAV_CAT(nav_mlp_rows_, NAV_MLP_PART)
+#endif
+int NAV_ROWS_NAME(int fam, int rt, int in_mode, int out_mode, const void* args, int n_nets,
+                  hipStream_t st) {
     return rt == 1 ? rows_rt<1>(fam, in_mode, out_mode, args, n_nets, st)
                    : rows_rt<2>(fam, in_mode, out_mode, args, n_nets, st);
 }
 
 // (a trace variant builds one part with NAV_PHASE_TRACE: tools/build_variant.sh)
-#if defined(NAV_PHASE_TRACE)
+#if defined(NAV_PHASE_TRACE) && !defined(NAV_MLP_POP)
 extern "C" int nav_phase_trace_read(unsigned long long* host, int n) {
     const size_t bytes = sizeof(g_phase_trace);
     if (!host || (size_t)n * sizeof(unsigned long long) < bytes) return NAV_EINVAL;
@@ -2219,7 +2312,7 @@ extern "C" int nav_phase_trace_read(unsigned long long* host, int n) {
 }
 #endif
 
-#if defined(NAV_CLOCK_STAMP) && NAV_MLP_PART == 8
+#if defined(NAV_CLOCK_STAMP) && NAV_MLP_PART == 8 && !defined(NAV_MLP_POP)
 extern "C" int nav_clock_stamp_read(unsigned long long* host, int n) {
     const size_t bytes = sizeof(g_clock_stamp);
     if (!host || (size_t)n * sizeof(unsigned long long) < bytes) return NAV_EINVAL;
@@ -2235,8 +2328,19 @@ namespace {
 // hp / 32 -> the per-NT object
 int rows_dispatch(int hp, int fam, int in_mode, int out_mode, const void* args, int n_nets,
                   int64_t M, hipStream_t st) {
-    const int rt = row_tiles_for(M, fam == FAM_FWD && out_mode == OUT_TICK);
+    const int rt = row_tiles_for(
+        M, fam == FAM_FWD && (out_mode == OUT_TICK || out_mode == OUT_TICK_POP));
     int r;
+    if (fam == FAM_TEST_POP || (fam == FAM_FWD && out_mode == OUT_TICK_POP)) {
+        decltype(&nav_mlp_rows_pop_1) const pop[8] = {
+            nav_mlp_rows_pop_1, nav_mlp_rows_pop_2, nav_mlp_rows_pop_3, nav_mlp_rows_pop_4,
+            nav_mlp_rows_pop_5, nav_mlp_rows_pop_6, nav_mlp_rows_pop_7, nav_mlp_rows_pop_8};
+        if (hp < 32 || hp > 256 || (hp & 31)) return NAV_EINVAL;
+        r = pop[hp / 32 - 1](fam, rt, in_mode, out_mode, args, n_nets, st);
+        if (r) return r;
+        NAV_CHECK_LAUNCH();
+        return 0;
+    }
     switch (hp / 32) {
         case 1: r = nav_mlp_rows_1(fam, rt, in_mode, out_mode, args, n_nets, st); break;
         case 2: r = nav_mlp_rows_2(fam, rt, in_mode, out_mode, args, n_nets, st); break;
@@ -2267,6 +2371,50 @@ int launch_bwd(const BwdArgs& a, int n_nets, hipStream_t st) {
         const int r_ = rows_dispatch((HP), (FAM), 0, 0, &(ARGS), 1, (ARGS).B, (ST));        \
         if (r_) return r_;                                                                  \
     }
+
+// ---- populations (nav_pop_table_build, nav_act_tick_pop, nav_test_rollout_pop) ----
+constexpr int kMaxMembers = 256;
+
+// One member's table entry, passed by value (stream-ordered, no host memory outlives the call).
+__global__ void k_pop_table_write(PopMember pm, PopMember* dst) {
+    static_assert(sizeof(PopMember) % 4 == 0, "copied as 32-bit words");
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(&pm);
+    uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+    for (int i = threadIdx.x; i < (int)(sizeof(PopMember) / 4); i += blockDim.x) d[i] = src[i];
+}
+
+// The host-side argument check the population entry points share (before any HIP call): n_envs =
+// n_members * envs_per_member, whole 64-row workgroups and (demo set given) whole demo groups per
+// member, one network shape, one set of the constants that key the Philox streams and the init,
+// one ring capacity >= envs_per_member (replays nullable: no rings). dev[m] receives member m's
+// actor.
+int pop_check(const nav_params* params, const nav_mlp* actors, const nav_replay* replays,
+              int32_t n_members, int32_t envs_per_member, const void* table, int64_t n_envs,
+              bool demo, int32_t envs_per_group, MlpDev* dev) {
+    if (!params || !actors || !table || n_members < 1 || n_members > kMaxMembers ||
+        envs_per_member < 64 || envs_per_member % 64 != 0 ||
+        n_envs != (int64_t)n_members * envs_per_member || n_envs >= ((int64_t)1 << 31))
+        return NAV_EINVAL;
+    if (demo && (envs_per_group <= 0 || envs_per_member % envs_per_group != 0))
+        return NAV_EINVAL;
+    for (int m = 0; m < n_members; ++m) {
+        const nav_mlp& a = actors[m];
+        const nav_params& p = params[m];
+        if (!make_dev(&a, &dev[m]) || a.d_in != 2 || a.d_out != 2) return NAV_EINVAL;
+        if (a.hidden != actors[0].hidden || a.hidden_pad != actors[0].hidden_pad ||
+            a.n_hidden != actors[0].n_hidden)
+            return NAV_EINVAL;
+        if (p.world_size != params[0].world_size ||
+            p.init_region_size != params[0].init_region_size ||
+            p.seed_lo != params[0].seed_lo || p.seed_hi != params[0].seed_hi ||
+            p.max_goal_draws != params[0].max_goal_draws)
+            return NAV_EINVAL;
+        if (replays && (!replays[m].rows || replays[m].capacity != replays[0].capacity ||
+                        replays[m].capacity < envs_per_member))
+            return NAV_EINVAL;
+    }
+    return 0;
+}
 
 }  // namespace
 
@@ -2383,6 +2531,106 @@ int nav_test_rollout(const nav_params* p, const nav_mlp* actor, const nav_env_so
     a.max_steps = max_steps;
     a.out = *out;
     return rows_dispatch(a.net.hp, FAM_TEST, 0, 0, &a, 1, a.n, S(stream));
+}
+
+int64_t nav_pop_table_bytes(int32_t n_members) {
+    if (n_members < 1 || n_members > kMaxMembers) return NAV_EINVAL;
+    return (int64_t)n_members * (int64_t)sizeof(PopMember);
+}
+
+int nav_pop_table_build(const nav_params* params, const nav_mlp* actors,
+                        const nav_replay* replays, int32_t n_members, int32_t envs_per_member,
+                        void* table, void* stream) {
+    MlpDev dev[kMaxMembers];
+    const int r = pop_check(params, actors, replays, n_members, envs_per_member, table,
+                            (int64_t)n_members * envs_per_member, false, 0, dev);
+    if (r) return r;
+    for (int m = 0; m < n_members; ++m) {
+        PopMember pm{};
+        pm.net = dev[m];
+        pm.p = params[m];
+        if (replays) {
+            const int64_t cap = replays[m].capacity;
+            pm.rows = reinterpret_cast<float4*>(replays[m].rows);
+            pm.base_off = (cap - ((int64_t)m * envs_per_member) % cap) % cap;
+        }
+        hipLaunchKernelGGL(k_pop_table_write, dim3(1), dim3(64), 0, S(stream), pm,
+                           static_cast<PopMember*>(table) + m);
+        NAV_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int nav_act_tick_pop(const nav_params* params, const nav_mlp* actors, const nav_replay* replays,
+                     int32_t n_members, int32_t envs_per_member, const void* table,
+                     const nav_env_soa* env, const float* field, const double* noise_z,
+                     uint32_t step, int32_t mode, int64_t replay_base, const nav_step_out* out,
+                     const double* demo_xy, const int64_t* demo_off, int32_t envs_per_group,
+                     const int64_t* cell_start, const int32_t* cand, double* action_out,
+                     double* reward_out, void* stream) {
+    MlpDev dev[kMaxMembers];
+    if (!env || !replays || (mode != 0 && mode != 1) || !field || !out || replay_base < 0)
+        return NAV_EINVAL;
+    const int r = pop_check(params, actors, replays, n_members, envs_per_member, table, env->n,
+                            demo_xy != nullptr, envs_per_group, dev);
+    if (r) return r;
+    if (!env->state || !env->goal || !env->region || !env->hist || !env->meta ||
+        !env->plan_index || !env->path_length || !env->episodes || !env->noise_scale)
+        return NAV_EINVAL;
+    const bool demo = demo_xy != nullptr;
+    if (demo && (!cell_start || !cand)) return NAV_EINVAL;
+    FwdArgs a{};
+    a.net[0] = dev[0];  // the common shape: picks the instantiation
+    a.p = params[0];    // the common seed of the noise draws
+    a.M = env->n;
+    a.state = env->state;
+    a.goal = env->goal;
+    a.noise_scale = env->noise_scale;
+    a.noise_z = noise_z;
+    a.step = step;
+    a.act_mode = mode;
+    a.action_out = action_out;
+    a.env = *env;
+    a.field = reinterpret_cast<const float2*>(field);
+    a.cap = replays[0].capacity;
+    a.base = replay_base % a.cap;
+    a.sout = *out;
+    if (demo)
+        a.demo = DemoIdx{reinterpret_cast<const double2*>(demo_xy), demo_off,
+                         envs_per_group > 0 ? envs_per_group : 1, cell_start, cand};
+    a.reward_out = reward_out;
+    a.pop = static_cast<const PopMember*>(table);
+    a.pop_blocks = envs_per_member / 64;
+    return launch_fwd<IN_BASELINE, OUT_TICK_POP>(a, 1, S(stream));
+}
+
+int nav_test_rollout_pop(const nav_params* params, const nav_mlp* actors, int32_t n_members,
+                         int32_t envs_per_member, const void* table, const nav_env_soa* env,
+                         const float* field, const double* start, uint32_t episode,
+                         int32_t max_steps, const nav_test_out* out, void* stream) {
+    MlpDev dev[kMaxMembers];
+    if (!env || !field || !out || max_steps < 1 || max_steps > (1 << 20)) return NAV_EINVAL;
+    const int r = pop_check(params, actors, nullptr, n_members, envs_per_member, table, env->n,
+                            false, 0, dev);
+    if (r) return r;
+    if (!env->goal || (!start && !env->region) || !out->reached || !out->steps ||
+        !out->best_distance || !out->final_state)
+        return NAV_EINVAL;
+    TestArgs a{};
+    a.net = dev[0];  // the common shape: picks the instantiation
+    a.n = env->n;
+    a.goal = reinterpret_cast<const double2*>(env->goal);
+    a.region = reinterpret_cast<const double4*>(env->region);
+    a.start = reinterpret_cast<const double2*>(start);
+    a.field = reinterpret_cast<const float2*>(field);
+    a.seed_lo = params[0].seed_lo;
+    a.seed_hi = params[0].seed_hi;
+    a.episode = episode;
+    a.max_steps = max_steps;
+    a.out = *out;
+    a.pop = static_cast<const PopMember*>(table);
+    a.pop_blocks = envs_per_member / (32 * row_tiles_for(a.n, false));
+    return rows_dispatch(a.net.hp, FAM_TEST_POP, 0, 0, &a, 1, a.n, S(stream));
 }
 
 int nav_mlp_forward(const nav_mlp* nets, int32_t n_nets, int64_t M, const float* in,

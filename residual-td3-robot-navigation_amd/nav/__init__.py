@@ -4,10 +4,12 @@ libnavenv.so (C-ABI: include/navenv.h), with the reference's Python API on top.
 
     from nav import Environment, Robot          # drop-ins for environment.py / robot.py
     from nav import VecEnv, VecTrainer, TD3     # the vectorised GPU path
+    from nav import PopulationTrainer, sweep_grid   # P configurations on one env set
 """
 from . import config  # noqa: F401
 
-__all__ = ["Environment", "Robot", "VecEnv", "VecTrainer", "TD3", "DeviceMLP", "ReplayRing"]
+__all__ = ["Environment", "Robot", "VecEnv", "VecTrainer", "TD3", "DeviceMLP", "ReplayRing",
+           "PopulationTrainer", "PopulationTable", "sweep_grid"]
 
 
 def __getattr__(name):
@@ -18,6 +20,9 @@ def __getattr__(name):
     if name == "VecTrainer":
         from .trainer import VecTrainer
         return VecTrainer
+    if name in ("PopulationTrainer", "PopulationTable", "sweep_grid"):
+        from . import population
+        return getattr(population, name)
     if name == "TD3":
         from .td3 import TD3
         return TD3

@@ -111,6 +111,16 @@ SIGNATURES = [
                                C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     ("nav_test_rollout", C.c_int, [_P(NavParams), _P(NavMlp), _P(NavEnvSoa), _vp, _vp,
                                    C.c_uint32, C.c_int32, _P(NavTestOut), _vp]),
+    ("nav_pop_table_bytes", C.c_int64, [C.c_int32]),
+    ("nav_pop_table_build", C.c_int, [_P(NavParams), _P(NavMlp), _P(NavReplay), C.c_int32,
+                                      C.c_int32, _vp, _vp]),
+    ("nav_act_tick_pop", C.c_int, [_P(NavParams), _P(NavMlp), _P(NavReplay), C.c_int32,
+                                   C.c_int32, _vp, _P(NavEnvSoa), _vp, _vp, C.c_uint32,
+                                   C.c_int32, C.c_int64, _P(NavStepOut), _vp, _vp, C.c_int32,
+                                   _vp, _vp, _vp, _vp, _vp]),
+    ("nav_test_rollout_pop", C.c_int, [_P(NavParams), _P(NavMlp), C.c_int32, C.c_int32, _vp,
+                                       _P(NavEnvSoa), _vp, _vp, C.c_uint32, C.c_int32,
+                                       _P(NavTestOut), _vp]),
     ("nav_mlp_forward", C.c_int, [_P(NavMlp), C.c_int32, C.c_int64, _vp, C.c_int32, C.c_int32,
                                   _P(_vp), C.c_int32, C.c_int32, C.c_int32, _vp, C.c_float,
                                   C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -176,7 +186,7 @@ SIGNATURES = [
 # Entry points that return int64 counts (negative = error) rather than a status code.
 _COUNT_FNS = {"nav_mlp_param_count", "nav_mlp_packed_count", "nav_mlp_mask_count",
               "nav_mlp_row_blocks", "nav_mlp_edge_count", "nav_mlp_hidden_count",
-              "nav_mlp_wgrad_splits", "nav_demo_index_res"}
+              "nav_mlp_wgrad_splits", "nav_demo_index_res", "nav_pop_table_bytes"}
 
 
 class NavError(RuntimeError):

@@ -75,9 +75,13 @@ class ReplayRing:
     """ReplayBuffer (robot.py:58-124) as a device ring of 32-byte rows
     (s0 s1 a0 a1 r s'0 s'1 done, float32)."""
 
-    def __init__(self, capacity, device="cuda"):
+    def __init__(self, capacity, device="cuda", rows=None):
         self.capacity = int(capacity)
-        self.rows = torch.zeros(self.capacity, 8, dtype=torch.float32, device=device)
+        if rows is None:
+            rows = torch.zeros(self.capacity, 8, dtype=torch.float32, device=device)
+        # (rows given: a [capacity][8] slice of a population's ring tensor)
+        assert rows.shape == (self.capacity, 8) and rows.is_contiguous()
+        self.rows = rows
         self.position = 0  # next write slot (robot.py:77)
         self.size = 0
 
@@ -253,7 +257,18 @@ class VecEnv:
         `start` [n][2] f64 gives the start states; None draws them from each env's init region on
         the test stream (NAV_TAG_TEST, `episode`). The tensors are allocated once per
         (max_steps, traj) and overwritten by the next call with the same pair."""
-        max_steps, key = int(max_steps), (int(max_steps), bool(traj))
+        max_steps = int(max_steps)
+        out, o = self._test_tensors(max_steps, traj, start)
+        a = actor.desc()
+        flops = max_steps * prof.mlp_fwd_flops(2, 2, actor.hidden, actor.n_hidden, self.n)
+        with prof.region("test_rollout", flops):
+            lib().nav_test_rollout(C.byref(self.p), C.byref(a), C.byref(self.soa),
+                                   ptr(self.field), ptr(start), int(episode) & 0xFFFFFFFF,
+                                   max_steps, C.byref(o), stream_handle(stream))
+        return out
+
+    def _test_tensors(self, max_steps, traj, start):
+        key = (max_steps, bool(traj))
         out = self._test_out.get(key)
         if out is None:
             d, n, f64 = self.device, self.n, torch.float64
@@ -266,14 +281,44 @@ class VecEnv:
             self._test_out[key] = out
         if start is not None:
             assert start.shape == (self.n, 2) and start.dtype == torch.float64
-        a = actor.desc()
         o = NavTestOut(*[ptr(out.get(k)) for k in ("reached", "steps", "best_distance",
                                                    "final_state", "traj")])
-        flops = max_steps * prof.mlp_fwd_flops(2, 2, actor.hidden, actor.n_hidden, self.n)
-        with prof.region("test_rollout", flops):
-            lib().nav_test_rollout(C.byref(self.p), C.byref(a), C.byref(self.soa),
-                                   ptr(self.field), ptr(start), int(episode) & 0xFFFFFFFF,
-                                   max_steps, C.byref(o), stream_handle(stream))
+        return out, o
+
+    # ---- populations (nav.population.PopulationTable): every member's launch form in one launch
+    # act_tick with member m's actor, constants and ring on its envs (nav_act_tick_pop). `base`
+    # is the rings' common write position; the caller advances the rings.
+    def act_tick_pop(self, pop, step, base, training=True, action_out=None, reward_out=None,
+                     noise_z=None, stream=None):
+        assert pop.n_members * pop.envs_per_member == self.n and pop.replays is not None
+        ix = self.demo_index if (self.demo_xy is not None and self.demo_xy.shape[0] > 0) else None
+        if self.demo_xy is not None and self.demo_xy.shape[0] > 0 and ix is None:
+            raise ValueError("act_tick_pop needs the demo index (set_demo(index=True))")
+        net = pop.nets[0]
+        flops = prof.mlp_fwd_flops(2, 2, net.hidden, net.n_hidden, self.n)
+        with prof.region("act_tick_pop", flops):
+            lib().nav_act_tick_pop(
+                pop.params, pop.actors, pop.replays, pop.n_members, pop.envs_per_member,
+                ptr(pop.table), C.byref(self.soa), ptr(self.field), ptr(noise_z),
+                int(step) & 0xFFFFFFFF, 0 if training else 1, int(base), C.byref(self.out),
+                ptr(self.demo_xy) if ix else None, ptr(self.demo_off) if ix else None,
+                self.envs_per_group, ptr(ix.cell_start) if ix else None,
+                ptr(ix.cand) if ix else None, ptr(action_out), ptr(reward_out),
+                stream_handle(stream))
+
+    # test_rollout with member m's actor, max_action and goal_threshold on its envs
+    # (nav_test_rollout_pop); the same output tensors as test_rollout
+    def test_rollout_pop(self, pop, max_steps, episode=0, start=None, traj=False, stream=None):
+        assert pop.n_members * pop.envs_per_member == self.n
+        max_steps = int(max_steps)
+        out, o = self._test_tensors(max_steps, traj, start)
+        net = pop.nets[0]
+        flops = max_steps * prof.mlp_fwd_flops(2, 2, net.hidden, net.n_hidden, self.n)
+        with prof.region("test_rollout_pop", flops):
+            lib().nav_test_rollout_pop(pop.params, pop.actors, pop.n_members,
+                                       pop.envs_per_member, ptr(pop.table), C.byref(self.soa),
+                                       ptr(self.field), ptr(start), int(episode) & 0xFFFFFFFF,
+                                       max_steps, C.byref(o), stream_handle(stream))
         return out
 
     def stats(self):

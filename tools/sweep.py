@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""Hyper-parameter sweep as one population (nav.population.PopulationTrainer): every configuration
+trains on its own member of one env set, all members act and tick in one launch and run their test
+episodes in one launch. Prints one JSON line per member: its overrides, its replica index and the
+numbers of evaluate().
+
+    python tools/sweep.py --reference-study
+    python tools/sweep.py --axis demo_factor=10,30,50,70 --replicas 2 --envs-per-member 4096 \\
+        --train-steps 200
+    python tools/sweep.py --axis initial_noise=1,0.5 --axis noise_decay=0.5,0.75,0.9 --replicas 3
+
+--reference-study runs the four DEMO_PROXIMITY_FACTOR values of the reference's published figure
+(average_score_by_demonstration_proximity.png); the second form is simulator.py:169-200's
+INITIAL_NOISE x NOISE_DECAY x 3 runs. Replica r of a configuration differs in its learner's seed
+(seed + r): initial weights, replay sampling and target-smoothing noise.
+"""
+import argparse
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, ".."))
+sys.path.insert(0, os.path.join(HERE, "..", "residual-td3-robot-navigation_amd"))
+
+REFERENCE_STUDY = {"demo_factor": [10.0, 30.0, 50.0, 70.0]}
+
+
+def parse_axis(text):
+    """'name=v1,v2,...' -> (name, [values]); ints stay ints, everything else is a float."""
+    name, _, values = text.partition("=")
+    if not name or not values:
+        raise argparse.ArgumentTypeError(f"--axis wants NAME=v1,v2,...: {text!r}")
+    out = []
+    for v in values.split(","):
+        try:
+            out.append(int(v))
+        except ValueError:
+            out.append(float(v))
+    return name, out
+
+
+def members_of(axes, replicas, seed):
+    from nav.population import sweep_grid
+    grid = sweep_grid(**axes)
+    if replicas == 1:
+        return [dict(m) for m in grid], [0] * len(grid)
+    members, replica = [], []
+    for m in grid:
+        for r in range(replicas):
+            members.append({**m, "seed": int(m.get("seed", seed)) + r})
+            replica.append(r)
+    return members, replica
+
+
+def main(argv=None):
+    from nav import config as K
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--axis", action="append", type=parse_axis, default=[],
+                    metavar="NAME=v1,v2,...", help="one swept override; repeat for a grid")
+    ap.add_argument("--reference-study", action="store_true",
+                    help="demo_factor over 10, 30, 50, 70 (the reference's figure)")
+    ap.add_argument("--replicas", type=int, default=1)
+    ap.add_argument("--envs-per-member", type=int, default=4096)
+    ap.add_argument("--envs-per-group", type=int, default=1024)
+    ap.add_argument("--train-steps", type=int, default=100)
+    ap.add_argument("--hidden", type=int, default=256)
+    ap.add_argument("--n-hidden", type=int, default=2)
+    ap.add_argument("--batch", type=int, default=None, help="default: envs per member")
+    ap.add_argument("--updates-per-step", type=int, default=2)
+    ap.add_argument("--streams", type=int, default=1)
+    ap.add_argument("--test-steps", type=int, default=K.TEST_TIMEOUT * K.UPDATE_RATE)
+    ap.add_argument("--seed", type=int, default=K.RANDOM_SEED)
+    ap.add_argument("--no-demos", action="store_true")
+    a = ap.parse_args(argv)
+    axes = dict(a.axis)
+    if a.reference_study:
+        axes = {**REFERENCE_STUDY, **axes}
+    if not axes:
+        ap.error("nothing to sweep: give --axis NAME=v1,v2,... or --reference-study")
+    if a.replicas < 1:
+        ap.error("--replicas must be at least 1")
+    members, replica = members_of(axes, a.replicas, a.seed)
+
+    from nav.population import PopulationTrainer
+    tr = PopulationTrainer(members, envs_per_member=a.envs_per_member, hidden=a.hidden,
+                           n_hidden=a.n_hidden, batch=a.batch or a.envs_per_member,
+                           updates_per_step=a.updates_per_step, seed=a.seed,
+                           envs_per_group=min(a.envs_per_group, a.envs_per_member),
+                           demos=not a.no_demos, streams=a.streams)
+    for _ in range(a.train_steps):
+        tr.step()
+    for m, row in enumerate(tr.evaluate(max_steps=a.test_steps)):
+        print(json.dumps({"member": m, "replica": replica[m], "train_steps": a.train_steps,
+                          **row}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
