@@ -90,11 +90,7 @@ inline size_t wgrad_lds_bytes() {
 // (k) when hp % 256 == 0 (NI = 8 column tiles of n, one 32-column half of k: every B operand
 // Q = g relu(h_0) is formed once per launch, where two 128 x 64 tiles with the same k0 formed it
 // twice), as 128 x 64 (NI = 4, two halves) when hp % 128 == 0, else 64 x 64. The path itself needs
-// a 2-hidden-layer network with whole 64 x 64 tiles. -DNAV_WGRAD_FACT_WIDE=0 (A/B only) keeps
-// 128 x 64 at hp % 256 == 0.
-#ifndef NAV_WGRAD_FACT_WIDE
-#define NAV_WGRAD_FACT_WIDE 1
-#endif
+// a 2-hidden-layer network with whole 64 x 64 tiles.
 __host__ __device__ inline bool wgrad_fact_ok(int hp, int n_hidden) {
     return n_hidden == 2 && hp % WG_TILE == 0;
 }
@@ -106,7 +102,7 @@ struct WgradTiling {
 inline WgradTiling wgrad_tiling(int d_out, int hp, int n_hidden) {
     WgradTiling t;
     const bool f1 = wgrad_fact_ok(hp, n_hidden) && d_out == 1;
-    const bool wide = NAV_WGRAD_FACT_WIDE && f1 && hp % 256 == 0;
+    const bool wide = f1 && hp % 256 == 0;
     t.tn = wide ? 256 : f1 && hp % 128 == 0 ? 128 : WG_TILE;
     t.tk = wide ? 32 : WG_TILE;
     t.TN = (hp + t.tn - 1) / t.tn;

@@ -20,25 +20,9 @@
 
 namespace {
 
-// 32-row blocks double-buffer the split stage and pass one barrier per k step (r03zt)
-constexpr bool kStageDb1 = true;
-// 32-row blocks split the whole layer's A once, then run the product without barriers
-// (gemm_cols_whole); NAV_WHOLE1=0 restores the per-step stage (A/B)
-#ifndef NAV_WHOLE1
-#define NAV_WHOLE1 1
-#endif
-constexpr bool kWholeStage1 = NAV_WHOLE1;
-// L2 warmer workgroups beside small row-kernel grids (warm_l2); NAV_WARM=0 for A/B
-#ifndef NAV_WARM
-#define NAV_WARM 1
-#endif
-[[maybe_unused]] constexpr bool kWarmL2 = NAV_WARM;
 // B-fragment prefetch distance (k steps) of the 64-row GEMMs in the critic row kernel and the
 // forward / tick kernels (the actor row kernel keeps 1: profiles/r05aq)
-#ifndef NAV_PF_WIDE
-#define NAV_PF_WIDE 2
-#endif
-constexpr int kPfWide = NAV_PF_WIDE;
+constexpr int kPfWide = 2;
 
 template <int NT>
 struct WaveCols {
@@ -66,21 +50,7 @@ NAV_DEV void publish_amax(float* slots, const float (&m)[RT]) {
     }
 }
 
-// acc[rt][j] = A[TM rows][hp] (LDS f32, row stride S_) x B[hp][tile t_j] on the fp16 matrix
-// cores at f32 accuracy (mlp_common.h: power-of-two scales, two-plane fp16 split, three
-// products). Per 16-deep k step the workgroup scales and splits the step's TM x 16 A values ONCE,
-// four per thread, into an LDS stage of two fp16 planes (split_stage), and every wave reads its
-// 16-B fragments from there (before: each of the 4 waves split every A value it read — the split
-// was ~15 % of the GEMM; probe r03v: -10 %). Two barriers per step: stage written, stage read. B is
-// the layer's image (split_entry layout, per-column exponents after the planes) in global
-// memory, L2-resident, its two planes loaded PF steps ahead. Lane (h, l32) holds A[row
-// l32][16q + 8h + j] and B[16q + 8h + j][col l32], j = 0..7 (the 32x32x16 operand maps). Every wave
-// runs the split and the barriers; waves without a column tile (NT < 4) skip only the MFMAs. The
-// result is unscaled before it is returned: the callers see acc = A . B in f32.
-#ifndef NAV_PF1
-#define NAV_PF1 2
-#endif
-constexpr int kPF1 = NAV_PF1;  // B prefetch distance of 32-row blocks
+constexpr int kPF1 = 2;  // B prefetch distance of 32-row blocks
 
 // gemm_cols for 32-row blocks (small batches, latency-bound): the workgroup scales and splits
 // the whole layer's 32 x hp A values into the whole-layer stage at once (two k steps per pass of
@@ -180,13 +150,21 @@ NAV_DEV void gemm_cols_whole(const float* __restrict__ A, int S_, const float* _
     }
 }
 
-template <int NT, int RT, int PFB = 1>
-NAV_DEV void gemm_cols(const float* __restrict__ A, int S_, const float* __restrict__ img,
-                       _Float16* stage, f32x16 (&acc)[RT][2]) {
-    if constexpr (RT == 1 && kWholeStage1) {
-        gemm_cols_whole<NT>(A, S_, img, stage, acc);
-        return;
-    }
+// acc[rt][j] = A[TM rows][hp] (LDS f32, row stride S_) x B[hp][tile t_j] on the fp16 matrix
+// cores at f32 accuracy (mlp_common.h: power-of-two scales, two-plane fp16 split, three
+// products). Per 16-deep k step the workgroup scales and splits the step's TM x 16 A values ONCE,
+// four per thread, into an LDS stage of two fp16 planes (split_stage), and every wave reads its
+// 16-B fragments from there (before: each of the 4 waves split every A value it read — the split
+// was ~15 % of the GEMM; probe r03v: -10 %). Two barriers per step: stage written, stage read. B is
+// the layer's image (split_entry layout, per-column exponents after the planes) in global
+// memory, L2-resident, its two planes loaded PF steps ahead. Lane (h, l32) holds A[row
+// l32][16q + 8h + j] and B[16q + 8h + j][col l32], j = 0..7 (the 32x32x16 operand maps). Every wave
+// runs the split and the barriers; waves without a column tile (NT < 4) skip only the MFMAs. The
+// result is unscaled before it is returned: the callers see acc = A . B in f32.
+template <int NT, int RT, int PF>
+NAV_DEV void gemm_cols_step(const float* __restrict__ A, int S_, const float* __restrict__ img,
+                            _Float16* stage, f32x16 (&acc)[RT][2]) {
+    static_assert(RT == 2, "the 64-row form only: 32-row blocks take gemm_cols_whole");
     constexpr int hp = NT * 32;
     constexpr int nq = hp / 16;
     constexpr int TM = RT * 32;
@@ -224,12 +202,9 @@ NAV_DEV void gemm_cols(const float* __restrict__ A, int S_, const float* __restr
     auto ldB = [&](uint32_t o, int p, int q) {
         return *reinterpret_cast<const f16x8*>(Bb + (o + (uint32_t)((p * PL + q * STEP) * 16)));
     };
-    // B planes PF steps ahead: one step for 64-row blocks (the register budget of the big row
-    // kernels), two for 32-row blocks, whose step (6 MFMAs per wave) is shorter than an L2 hit
-    // B prefetch distance in k steps: 64-row blocks take the caller's PFB (2 in the critic row
-    // kernel and the forward / tick launches, 1 in the 256-register actor row kernel, where a
-    // second step of B fragments costs more than it hides: profiles/r05ap)
-    constexpr int PF = RT == 1 ? kPF1 : PFB;
+    // B planes PF steps ahead, the caller's choice: 2 in the critic row kernel and the forward /
+    // tick launches, 1 in the 256-register actor row kernel, where a second step of B fragments
+    // costs more than it hides (profiles/r05ap)
     f16x8 bq0[PF + 1][2], bq1[PF + 1][2];
 #pragma unroll
     for (int d = 0; d < PF; ++d)
@@ -243,34 +218,26 @@ NAV_DEV void gemm_cols(const float* __restrict__ A, int S_, const float* __restr
     // halves of row r are swapped when (r >> 3) & 1, which makes both the 8-B stores and the
     // waves' 16-B fragment reads bank-conflict-free (ds_read_b128 lane groups). With 64 rows
     // every thread has a share (no branch: the split sits in the MFMAs' basic block)
-    const bool sp = TM * 4 >= kBlock || tid < TM * 4;
+    static_assert(TM * 4 == kBlock, "one share per thread");
     const int sr = tid >> 2, sk = (tid & 3) * 4;
     const float* src = A + sr * S_ + sk;
     _Float16* dst = stage + sr * 16 + ((((sk >> 3) ^ (sr >> 3)) & 1) << 3) + (sk & 7);
     const _Float16* frag = stage + l32 * 16 + (((h ^ (l32 >> 3)) & 1) << 3);
-    float4 x = sp ? *reinterpret_cast<const float4*>(src) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float sa = ldexpf(1.f, RT == 1 ? ea[0] : ea[(sr >> 5) < RT ? (sr >> 5) : RT - 1]);
+    float4 x = *reinterpret_cast<const float4*>(src);
+    const float sa = ldexpf(1.f, ea[(sr >> 5) < RT ? (sr >> 5) : RT - 1]);
     // scale + split of step q's share (x) into the stage, the next x from the LDS rows, B planes
-    // ahead. 32-row blocks (small batches: latency-bound, one wave per SIMD) double-buffer the
-    // stage and pass one barrier per step: step q + 1's stores go to the buffer step q - 1 was
-    // read from, which every wave finished reading (and consumed in its MFMAs) before step q's
-    // barrier
-    constexpr bool DB = RT == 1 && kStageDb1;
-    constexpr int SB = 2 * PP;  // fp16 per stage buffer
+    // ahead
     auto produce = [&](int q) {
-        if (sp) {
-            _Float16* const dq = dst + (DB ? (q & 1) * SB : 0);
-            const float v[4] = {x.x * sa, x.y * sa, x.z * sa, x.w * sa};
-            f16x4 ph, pl;
+        const float v[4] = {x.x * sa, x.y * sa, x.z * sa, x.w * sa};
+        f16x4 ph, pl;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) ph[j] = (_Float16)v[j];
-            pin_value(ph);  // lo from the stored hi's bits (mlp_common.h)
+        for (int j = 0; j < 4; ++j) ph[j] = (_Float16)v[j];
+        pin_value(ph);  // lo from the stored hi's bits (mlp_common.h)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) pl[j] = (_Float16)(v[j] - (float)ph[j]);
-            *reinterpret_cast<f16x4*>(dq) = ph;
-            *reinterpret_cast<f16x4*>(dq + PP) = pl;
-            if (q + 1 < nq) x = *reinterpret_cast<const float4*>(src + 16 * (q + 1));
-        }
+        for (int j = 0; j < 4; ++j) pl[j] = (_Float16)(v[j] - (float)ph[j]);
+        *reinterpret_cast<f16x4*>(dst) = ph;
+        *reinterpret_cast<f16x4*>(dst + PP) = pl;
+        if (q + 1 < nq) x = *reinterpret_cast<const float4*>(src + 16 * (q + 1));
         // production of step q runs during step q - 1's MFMAs: the B planes loaded here are
         // step q - 1 + PF's (steps 0 .. PF - 1 come from the prologue)
         const int qb = q - 1 + PF;
@@ -283,21 +250,19 @@ NAV_DEV void gemm_cols(const float* __restrict__ A, int S_, const float* __restr
         }
     };
     Split2 sa2[RT];
-    // two barriers per step (one buffer): the stage is written, then read (the next step may
-    // overwrite it); one barrier with the double buffer
-    auto consume = [&](int q) {
+    // two barriers per step: the stage is written, then read (the next step may overwrite it)
+    auto consume = [&]() {
         __syncthreads();
-        const _Float16* fq = frag + (DB ? (q & 1) * SB : 0);
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
-            const _Float16* f = fq + rt * 32 * 16;
+            const _Float16* f = frag + rt * 32 * 16;
             sa2[rt].h = *reinterpret_cast<const f16x8*>(f);
             sa2[rt].l = *reinterpret_cast<const f16x8*>(f + PP);
         }
-        if (!DB) __syncthreads();
+        __syncthreads();
     };
     produce(0);
-    consume(0);
+    consume();
     // Two workgroups share a CU at the bench shapes (blocks b and b + kCUs, dispatched together),
     // and at equal priority the SIMD arbiter issues the older wave first: the second workgroup's
     // GEMMs lag and it ends its last ~50 k cycles alone at the lone-workgroup MFMA rate (critic_rows:
@@ -322,7 +287,7 @@ NAV_DEV void gemm_cols(const float* __restrict__ A, int S_, const float* __restr
                     acc[rt][1] = mfma_x3(cur[rt], bq1[q % (PF + 1)], acc[rt][1]);
             }
         }
-        if (q + 1 < nq) consume(q + 1);
+        if (q + 1 < nq) consume();
     }
     if (favored) __builtin_amdgcn_s_setprio(0);
     // unscale: acc 2^-(ea[rt] + e_n), exact (v_ldexp_f32)
@@ -335,6 +300,17 @@ NAV_DEV void gemm_cols(const float* __restrict__ A, int S_, const float* __restr
             acc[rt][1][i] = ldexpf(acc[rt][1][i], u1);
         }
     }
+}
+
+// 32-row blocks take the whole-layer stage, 64-row blocks the per-step stage with the caller's B
+// prefetch distance
+template <int NT, int RT, int PFB = 1>
+NAV_DEV void gemm_cols(const float* __restrict__ A, int S_, const float* __restrict__ img,
+                       _Float16* stage, f32x16 (&acc)[RT][2]) {
+    if constexpr (RT == 1)
+        gemm_cols_whole<NT>(A, S_, img, stage, acc);
+    else
+        gemm_cols_step<NT, RT, PFB>(A, S_, img, stage, acc);
 }
 
 // ---- the top hidden layer's row backward of a d_out = 1 network on its ReLU bits ----
@@ -467,7 +443,8 @@ NAV_DEV void gemm_bits(const float* scr, const float* __restrict__ img, f32x16 (
     auto ldB = [&](uint32_t o, int p, int q) {
         return *reinterpret_cast<const f16x8*>(Bb + (o + (uint32_t)((p * PL + q * STEP) * 16)));
     };
-    // B prefetch distance in k steps as gemm_cols
+    // B prefetch distance in k steps: kPF1 for 32-row blocks as in gemm_cols_whole, the caller's
+    // for 64-row blocks as in gemm_cols_step
     constexpr int PF = RT == 1 ? kPF1 : PFB;
     f16x8 bq0[PF + 1][2], bq1[PF + 1][2];
 #pragma unroll
@@ -632,16 +609,18 @@ struct FwdArgs {
 // Output-layer partial sums: [d_out <= 2][4 waves][TM rows] (red_floats per block).
 __host__ __device__ constexpr int red_floats(int tm) { return 2 * kWaves * tm; }
 
-// bytes of gemm_cols' split stage for TM rows: [2 planes][TM][16] fp16 (two buffers for 32-row
-// blocks), then the kWaves amax slots
+// fp16 of gemm_cols_step's split stage for TM rows: [2 planes][TM][16], then the kWaves amax
+// slots. A 32-row block keeps a region of the same size (two 32-row buffers, from the per-step
+// form it once ran) ahead of its slots and never touches it: moving the slots would change every
+// 32-row kernel's LDS immediates
 __host__ __device__ constexpr size_t stage_halves(int tm) {
-    return (size_t)(tm == 32 && kStageDb1 ? 2 : 1) * 2 * tm * 16;
+    return (size_t)(tm == 32 ? 2 : 1) * 2 * tm * 16;
 }
 // 32-row blocks also take the whole-layer stage past the slots (gemm_cols_whole): [hp / 16 k
 // steps][2 planes][32][16] fp16, hp * 128 bytes
 __host__ __device__ constexpr size_t stage_bytes(int tm, int hp) {
     return stage_halves(tm) * 2 + 4 * kWaves * (tm / 32) +
-           (tm == 32 && kWholeStage1 ? (size_t)hp * 128 : 0);
+           (tm == 32 ? (size_t)hp * 128 : 0);
 }
 template <int TM>
 NAV_DEV float* amax_slots(_Float16* stage) {
@@ -2192,7 +2171,7 @@ void launch_critic_rows_k(const CriticRowsArgs& a, hipStream_t st) {
     // the images in the order the compute workgroups consume them (targets: forward only)
     CriticRowsArgs w = a;
     w.warm = WarmList{};
-    bool ok = kWarmL2 && warm_net(w.warm, a.actor_t, true) && warm_net(w.warm, a.critic_t[0], true) &&
+    bool ok = warm_net(w.warm, a.actor_t, true) && warm_net(w.warm, a.critic_t[0], true) &&
               warm_net(w.warm, a.critic_t[1], true) && warm_net(w.warm, a.critic[0], false) &&
               warm_net(w.warm, a.critic[1], false);
     if (!ok) w.warm.n = 0;
@@ -2213,7 +2192,7 @@ void launch_actor_rows_k(const ActorRowsArgs& a, hipStream_t st) {
     const unsigned gx = (unsigned)((a.B + TM - 1) / TM);
     ActorRowsArgs w = a;
     w.warm = WarmList{};
-    const bool ok = kWarmL2 && warm_net(w.warm, a.actor, false) && warm_net(w.warm, a.critic, false);
+    const bool ok = warm_net(w.warm, a.actor, false) && warm_net(w.warm, a.critic, false);
     if (!ok) w.warm.n = 0;
     w.warm.y0 = 1;
     const unsigned wy = warm_rows(w.warm, gx, 1u);
@@ -2325,33 +2304,20 @@ extern "C" int nav_clock_stamp_read(unsigned long long* host, int n) {
 
 namespace {
 
-// hp / 32 -> the per-NT object
+// hp / 32 -> the per-NT object; the population forms of the tick and the test rollout live in
+// objects of their own (row 1)
 int rows_dispatch(int hp, int fam, int in_mode, int out_mode, const void* args, int n_nets,
                   int64_t M, hipStream_t st) {
+    static decltype(&nav_mlp_rows_1) const rows[2][8] = {
+        {nav_mlp_rows_1, nav_mlp_rows_2, nav_mlp_rows_3, nav_mlp_rows_4, nav_mlp_rows_5,
+         nav_mlp_rows_6, nav_mlp_rows_7, nav_mlp_rows_8},
+        {nav_mlp_rows_pop_1, nav_mlp_rows_pop_2, nav_mlp_rows_pop_3, nav_mlp_rows_pop_4,
+         nav_mlp_rows_pop_5, nav_mlp_rows_pop_6, nav_mlp_rows_pop_7, nav_mlp_rows_pop_8}};
     const int rt = row_tiles_for(
         M, fam == FAM_FWD && (out_mode == OUT_TICK || out_mode == OUT_TICK_POP));
-    int r;
-    if (fam == FAM_TEST_POP || (fam == FAM_FWD && out_mode == OUT_TICK_POP)) {
-        decltype(&nav_mlp_rows_pop_1) const pop[8] = {
-            nav_mlp_rows_pop_1, nav_mlp_rows_pop_2, nav_mlp_rows_pop_3, nav_mlp_rows_pop_4,
-            nav_mlp_rows_pop_5, nav_mlp_rows_pop_6, nav_mlp_rows_pop_7, nav_mlp_rows_pop_8};
-        if (hp < 32 || hp > 256 || (hp & 31)) return NAV_EINVAL;
-        r = pop[hp / 32 - 1](fam, rt, in_mode, out_mode, args, n_nets, st);
-        if (r) return r;
-        NAV_CHECK_LAUNCH();
-        return 0;
-    }
-    switch (hp / 32) {
-        case 1: r = nav_mlp_rows_1(fam, rt, in_mode, out_mode, args, n_nets, st); break;
-        case 2: r = nav_mlp_rows_2(fam, rt, in_mode, out_mode, args, n_nets, st); break;
-        case 3: r = nav_mlp_rows_3(fam, rt, in_mode, out_mode, args, n_nets, st); break;
-        case 4: r = nav_mlp_rows_4(fam, rt, in_mode, out_mode, args, n_nets, st); break;
-        case 5: r = nav_mlp_rows_5(fam, rt, in_mode, out_mode, args, n_nets, st); break;
-        case 6: r = nav_mlp_rows_6(fam, rt, in_mode, out_mode, args, n_nets, st); break;
-        case 7: r = nav_mlp_rows_7(fam, rt, in_mode, out_mode, args, n_nets, st); break;
-        case 8: r = nav_mlp_rows_8(fam, rt, in_mode, out_mode, args, n_nets, st); break;
-        default: return NAV_EINVAL;
-    }
+    const bool pop = fam == FAM_TEST_POP || (fam == FAM_FWD && out_mode == OUT_TICK_POP);
+    if (hp < 32 || hp > 256 || (hp & 31)) return NAV_EINVAL;
+    const int r = rows[pop][hp / 32 - 1](fam, rt, in_mode, out_mode, args, n_nets, st);
     if (r) return r;
     NAV_CHECK_LAUNCH();
     return 0;
@@ -2366,11 +2332,54 @@ int launch_bwd(const BwdArgs& a, int n_nets, hipStream_t st) {
     return rows_dispatch(a.net[0].hp, FAM_BWD, 0, 0, &a, n_nets, a.M, st);
 }
 
-#define NAV_ROWS_SWITCH(HP, FAM, ARGS, ST)                                                  \
-    {                                                                                       \
-        const int r_ = rows_dispatch((HP), (FAM), 0, 0, &(ARGS), 1, (ARGS).B, (ST));        \
-        if (r_) return r_;                                                                  \
-    }
+// ---- what nav_act_tick / nav_act_tick_pop and nav_test_rollout / nav_test_rollout_pop share ----
+// the env arrays a tick reads or writes, and the cell index beside a demo set
+bool tick_ptrs_ok(const nav_env_soa* env, const double* demo_xy, const int64_t* cell_start,
+                  const int32_t* cand) {
+    if (!env->state || !env->goal || !env->region || !env->hist || !env->meta ||
+        !env->plan_index || !env->path_length || !env->episodes || !env->noise_scale)
+        return false;
+    return !demo_xy || (cell_start && cand);
+}
+
+void fill_tick(FwdArgs& a, const nav_env_soa* env, const float* field, const double* noise_z,
+               uint32_t step, int32_t mode, const nav_step_out* out, const double* demo_xy,
+               const int64_t* demo_off, int32_t envs_per_group, const int64_t* cell_start,
+               const int32_t* cand, double* action_out, double* reward_out) {
+    a.M = env->n;
+    a.state = env->state;
+    a.goal = env->goal;
+    a.noise_scale = env->noise_scale;
+    a.noise_z = noise_z;
+    a.step = step;
+    a.act_mode = mode;
+    a.action_out = action_out;
+    a.env = *env;
+    a.field = reinterpret_cast<const float2*>(field);
+    a.sout = *out;
+    if (demo_xy)
+        a.demo = DemoIdx{reinterpret_cast<const double2*>(demo_xy), demo_off,
+                         envs_per_group > 0 ? envs_per_group : 1, cell_start, cand};
+    a.reward_out = reward_out;
+}
+
+// the env arrays a test rollout reads (region only without given starts) and its outputs
+bool test_ptrs_ok(const nav_env_soa* env, const double* start, const nav_test_out* out) {
+    return env->goal && (start || env->region) && out->reached && out->steps &&
+           out->best_distance && out->final_state;
+}
+
+void fill_test(TestArgs& a, const nav_env_soa* env, const float* field, const double* start,
+               uint32_t episode, int32_t max_steps, const nav_test_out* out) {
+    a.n = env->n;
+    a.goal = reinterpret_cast<const double2*>(env->goal);
+    a.region = reinterpret_cast<const double4*>(env->region);
+    a.start = reinterpret_cast<const double2*>(start);
+    a.field = reinterpret_cast<const float2*>(field);
+    a.episode = episode;
+    a.max_steps = max_steps;
+    a.out = *out;
+}
 
 // ---- populations (nav_pop_table_build, nav_act_tick_pop, nav_test_rollout_pop) ----
 constexpr int kMaxMembers = 256;
@@ -2478,31 +2487,14 @@ int nav_act_tick(const nav_params* p, const nav_mlp* actor, const nav_env_soa* e
         replay->capacity <= 0 || replay_base < 0 || (demo_off && envs_per_group <= 0))
         return NAV_EINVAL;
     if (env->n == 0) return 0;
-    if (!env->state || !env->goal || !env->region || !env->hist || !env->meta ||
-        !env->plan_index || !env->path_length || !env->episodes || !env->noise_scale)
-        return NAV_EINVAL;
-    const bool demo = demo_xy != nullptr;
-    if (demo && (!cell_start || !cand)) return NAV_EINVAL;
-    a.M = env->n;
-    a.state = env->state;
-    a.goal = env->goal;
-    a.noise_scale = env->noise_scale;
-    a.noise_z = noise_z;
-    a.step = step;
-    a.act_mode = mode;
+    if (!tick_ptrs_ok(env, demo_xy, cell_start, cand)) return NAV_EINVAL;
+    fill_tick(a, env, field, noise_z, step, mode, out, demo_xy, demo_off, envs_per_group,
+              cell_start, cand, action_out, reward_out);
     a.max_action_d = p->max_action;
-    a.action_out = action_out;
     a.p = *p;
-    a.env = *env;
-    a.field = reinterpret_cast<const float2*>(field);
     a.rows = reinterpret_cast<float4*>(replay->rows);
     a.cap = replay->capacity;
     a.base = replay_base % replay->capacity;
-    a.sout = *out;
-    if (demo)
-        a.demo = DemoIdx{reinterpret_cast<const double2*>(demo_xy), demo_off,
-                         envs_per_group > 0 ? envs_per_group : 1, cell_start, cand};
-    a.reward_out = reward_out;
     return launch_fwd<IN_BASELINE, OUT_TICK>(a, 1, S(stream));
 }
 
@@ -2515,21 +2507,12 @@ int nav_test_rollout(const nav_params* p, const nav_mlp* actor, const nav_env_so
         env->n >= ((int64_t)1 << 31))
         return NAV_EINVAL;
     if (env->n == 0) return 0;
-    if (!env->goal || (!start && !env->region) || !out->reached || !out->steps ||
-        !out->best_distance || !out->final_state)
-        return NAV_EINVAL;
-    a.n = env->n;
-    a.goal = reinterpret_cast<const double2*>(env->goal);
-    a.region = reinterpret_cast<const double4*>(env->region);
-    a.start = reinterpret_cast<const double2*>(start);
-    a.field = reinterpret_cast<const float2*>(field);
+    if (!test_ptrs_ok(env, start, out)) return NAV_EINVAL;
+    fill_test(a, env, field, start, episode, max_steps, out);
     a.max_action = p->max_action;
     a.goal_threshold = p->goal_threshold;
     a.seed_lo = p->seed_lo;
     a.seed_hi = p->seed_hi;
-    a.episode = episode;
-    a.max_steps = max_steps;
-    a.out = *out;
     return rows_dispatch(a.net.hp, FAM_TEST, 0, 0, &a, 1, a.n, S(stream));
 }
 
@@ -2574,31 +2557,14 @@ int nav_act_tick_pop(const nav_params* params, const nav_mlp* actors, const nav_
     const int r = pop_check(params, actors, replays, n_members, envs_per_member, table, env->n,
                             demo_xy != nullptr, envs_per_group, dev);
     if (r) return r;
-    if (!env->state || !env->goal || !env->region || !env->hist || !env->meta ||
-        !env->plan_index || !env->path_length || !env->episodes || !env->noise_scale)
-        return NAV_EINVAL;
-    const bool demo = demo_xy != nullptr;
-    if (demo && (!cell_start || !cand)) return NAV_EINVAL;
+    if (!tick_ptrs_ok(env, demo_xy, cell_start, cand)) return NAV_EINVAL;
     FwdArgs a{};
+    fill_tick(a, env, field, noise_z, step, mode, out, demo_xy, demo_off, envs_per_group,
+              cell_start, cand, action_out, reward_out);
     a.net[0] = dev[0];  // the common shape: picks the instantiation
     a.p = params[0];    // the common seed of the noise draws
-    a.M = env->n;
-    a.state = env->state;
-    a.goal = env->goal;
-    a.noise_scale = env->noise_scale;
-    a.noise_z = noise_z;
-    a.step = step;
-    a.act_mode = mode;
-    a.action_out = action_out;
-    a.env = *env;
-    a.field = reinterpret_cast<const float2*>(field);
     a.cap = replays[0].capacity;
     a.base = replay_base % a.cap;
-    a.sout = *out;
-    if (demo)
-        a.demo = DemoIdx{reinterpret_cast<const double2*>(demo_xy), demo_off,
-                         envs_per_group > 0 ? envs_per_group : 1, cell_start, cand};
-    a.reward_out = reward_out;
     a.pop = static_cast<const PopMember*>(table);
     a.pop_blocks = envs_per_member / 64;
     return launch_fwd<IN_BASELINE, OUT_TICK_POP>(a, 1, S(stream));
@@ -2613,21 +2579,12 @@ int nav_test_rollout_pop(const nav_params* params, const nav_mlp* actors, int32_
     const int r = pop_check(params, actors, nullptr, n_members, envs_per_member, table, env->n,
                             false, 0, dev);
     if (r) return r;
-    if (!env->goal || (!start && !env->region) || !out->reached || !out->steps ||
-        !out->best_distance || !out->final_state)
-        return NAV_EINVAL;
+    if (!test_ptrs_ok(env, start, out)) return NAV_EINVAL;
     TestArgs a{};
+    fill_test(a, env, field, start, episode, max_steps, out);
     a.net = dev[0];  // the common shape: picks the instantiation
-    a.n = env->n;
-    a.goal = reinterpret_cast<const double2*>(env->goal);
-    a.region = reinterpret_cast<const double4*>(env->region);
-    a.start = reinterpret_cast<const double2*>(start);
-    a.field = reinterpret_cast<const float2*>(field);
     a.seed_lo = params[0].seed_lo;
     a.seed_hi = params[0].seed_hi;
-    a.episode = episode;
-    a.max_steps = max_steps;
-    a.out = *out;
     a.pop = static_cast<const PopMember*>(table);
     a.pop_blocks = envs_per_member / (32 * row_tiles_for(a.n, false));
     return rows_dispatch(a.net.hp, FAM_TEST_POP, 0, 0, &a, 1, a.n, S(stream));
@@ -2791,9 +2748,7 @@ int nav_td3_critic_rows(const nav_mlp* target_actor, const nav_mlp* target_criti
     a.batch = batch;
     a.ecount = edge_count(a.critic[0]);
     a.save_mask = save_mask;
-    NAV_ROWS_SWITCH(a.actor_t.hp, FAM_CRITIC, a, S(stream))
-    NAV_CHECK_LAUNCH();
-    return 0;
+    return rows_dispatch(a.actor_t.hp, FAM_CRITIC, 0, 0, &a, 1, a.B, S(stream));
 }
 
 int nav_td3_actor_rows(const nav_mlp* actor, const nav_mlp* critic, const nav_replay* replay,
@@ -2830,9 +2785,7 @@ int nav_td3_actor_rows(const nav_mlp* actor, const nav_mlp* critic, const nav_re
     a.masks_c = masks_critic;
     a.eslab = edge_slabs;
     a.ecount = edge_count(a.actor);
-    NAV_ROWS_SWITCH(a.actor.hp, FAM_ACTOR, a, S(stream))
-    NAV_CHECK_LAUNCH();
-    return 0;
+    return rows_dispatch(a.actor.hp, FAM_ACTOR, 0, 0, &a, 1, a.B, S(stream));
 }
 
 int64_t nav_mlp_mask_count(int32_t hidden_pad, int32_t n_hidden, int64_t M) {

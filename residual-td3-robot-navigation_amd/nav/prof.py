@@ -1,9 +1,11 @@
 """Per-kernel timing with HIP events on the launch stream, and the algorithmic work counts the
 roofline figures use.
 
-`with timing(KernelTimer(...)):` activates a timer; every libnavenv launch site in nav/ wraps its
-launch in `region(name, work)`, which records a start/stop event pair on the current stream (the
-stream the kernel is launched on) when the timer tracks that name. Nothing is recorded otherwise.
+`with timing(KernelTimer(...)):` activates a timer; the timed libnavenv launch sites in nav/ issue
+their launch inside `region(name, work)` (the learner's through `TD3._run`: the same call with the
+same arguments, entered directly while no timer is active), which records a start/stop event pair
+on the current stream (the stream the kernel is launched on) when the timer tracks that name.
+Nothing is recorded otherwise.
 The events are libnavenv's device-scope-release HIP events (nav_event_*): a default HIP event
 record costs ~6 us of GPU time (system-scope L2 writeback), which would stretch the timed region.
 """

@@ -48,8 +48,7 @@ class _Adam:
 
 class TD3:
     def __init__(self, cfg=None, device="cuda", seed=K.RANDOM_SEED, actor=None, critic1=None,
-                 critic2=None, grad_hook=None, row_backward=True, fuse_soft_update=True,
-                 wgrad_splits=None):
+                 critic2=None, grad_hook=None, wgrad_splits=None):
         self.cfg = cfg or K.TD3Config()
         c = self.cfg
         nc = c.net
@@ -80,12 +79,6 @@ class TD3:
                 raise ValueError("grad_hook must carry an int world_size >= 1: it SUM-all-reduces "
                                  "the gradient bucket and Adam divides by world_size")
             self.grad_div = float(ws)
-        # train_critic's row backward inside the critic_rows launch (False: its own launch; the
-        # results are bit-identical, A/B only)
-        self.row_backward = bool(row_backward)
-        # a policy epoch's soft updates inside the actor's reduce + Adam launch (False: their own
-        # launch; A/B only)
-        self.fuse_soft_update = bool(fuse_soft_update)
         # row splits of the weight-gradient launches, (critic twins, actor); None = as many as
         # fill the chip (nav_mlp_wgrad_splits; tuning only)
         self.wgrad_splits = wgrad_splits
@@ -93,8 +86,8 @@ class TD3:
         # (1 / 0 force either form; the results are bit-identical)
         self.split_twins = -1
         self._B = 0
-        # the per-epoch launches' constant ctypes arguments (_static), rebuilt when the batch
-        # size, the seed or a hyper-parameter they carry changes (_static_key)
+        # every launch's constant ctypes arguments and work counts (_static), rebuilt when the
+        # batch size, the seed or a hyper-parameter they carry changes (its key)
         self._st = None
         self._st_key = None
         self._rd = (None, None)
@@ -143,149 +136,85 @@ class TD3:
         self._B = B
         self._st = None
 
-    def _wgrad(self, nets, M, inp, ld_in, in_col, acts, dz, dy, ld_dy, masks, hslabs, s):
-        """Hidden x hidden weight gradients of 1-2 same-shape nets: one MFMA launch writing
-        `splits` partial slabs per net."""
-        net = nets[0]
-        splits = self.splits_a if net is self.actor_network else self.splits_c
-        if net.n_hidden > 1:
-            # k_wgrad_fact (d_out 1, 2 hidden layers, whole 64-wide tiles: 2 fp16 products per
-            # f32 product) is timed apart from k_wgrad (3 products): their rooflines differ
-            fact = net.d_out == 1 and net.n_hidden == 2 and net.hp % 64 == 0
-            with prof.region("mlp_wgrad_fact" if fact else "mlp_wgrad",
-                             len(nets) * prof.mlp_wgrad_flops(net.hidden, net.n_hidden, M)):
-                lib().nav_mlp_wgrad(descs(*nets), len(nets), M, ptr(inp), ld_in, in_col,
-                                    parr(*acts), parr(*dz), parr(*dy), ld_dy, parr(*masks),
-                                    parr(*hslabs), splits, s)
-        return splits
+    # ---- the launches. Each is issued in one place, with its constant arguments and its work
+    # count built once in _static (the small-batch learner of config 1 is bound by the host's
+    # issue of ~450 launches per td3_update), through _run: timed or not, the same call
+    def _run(self, name, work, fn, *args):
+        """fn(*args), as the region `name` of an active timer (nav.prof) if there is one."""
+        if prof._active is None:
+            return fn(*args)
+        with prof.region(name, work):
+            return fn(*args)
 
     def _reduce_bytes(self, nets, eslabs, splits, adam):
         return sum(4.0 * (splits * (x.count - e.shape[1]) + e.numel() +
                           (4 if adam else 1) * x.count) for x, e in zip(nets, eslabs))
 
-    def _hook_and_adam(self, nets, opts, grads, s, stream, soft_update):
-        self._hook(self.grad_c if len(nets) == 2 else grads[0], stream)
-        self._adam(nets, opts, grads, s, self.grad_div)
-        if soft_update:
-            self.soft_update_all(stream)
-
-    def _grads_and_step(self, nets, opts, M, inp, ld_in, in_col, acts, dz, dy, ld_dy, masks,
-                        eslabs, grads, hslabs, s, stream, soft_update=False):
-        """Weight gradients (nav_mlp_wgrad), then the fixed-order reduce of those and the fwd/bwd
-        edge partials fused with each net's Adam step (robot.py:236-239) of 1-2 nets (and on a
-        policy epoch the three soft updates). With a grad_hook (shared policy) the reduce writes
-        the flat gradient bucket without Adam, the hook all-reduces it, and one multi-net Adam
-        launch applies bucket / world_size."""
-        splits = self._wgrad(nets, M, inp, ld_in, in_col, acts, dz, dy, ld_dy, masks, hslabs, s)
-        if self.grad_hook is None:
-            coeffs = [o.advance() for o in opts]
-            args = (descs(*nets), len(nets), parr(*hslabs), splits, parr(*eslabs), self.nblk,
-                    parr(*grads), parr(*[o.m for o in opts]), parr(*[o.v for o in opts]),
-                    opts[0].b1, opts[0].b2, opts[0].eps,
-                    (C.c_float * len(nets))(*[c[0] for c in coeffs]),
-                    (C.c_float * len(nets))(*[c[1] for c in coeffs]))
-            with prof.region("grad_reduce", self._reduce_bytes(nets, eslabs, splits, True)):
-                if soft_update:  # the actor's step and all three soft updates in one launch
-                    lib().nav_grad_reduce_adam_polyak(
-                        *args, descs(self.target_actor),
-                        descs(self.target_critic_network_1, self.target_critic_network_2),
-                        descs(self.critic_network_1, self.critic_network_2), 2, self.cfg.tau, s)
-                else:
-                    lib().nav_grad_reduce_adam(*args, s)
-            return
-        with prof.region("grad_reduce", self._reduce_bytes(nets, eslabs, splits, False)):
-            lib().nav_grad_reduce_multi(descs(*nets), len(nets), parr(*hslabs), splits,
-                                        parr(*eslabs), self.nblk, parr(*grads), s)
-        self._hook_and_adam(nets, opts, grads, s, stream, soft_update)
-
-    def _adam(self, nets, opts, grads, s, grad_div=1.0):
-        """One multi-net Adam launch on flat gradients (already reduced) / grad_div."""
-        coeffs = [o.advance() for o in opts]
-        n = len(nets)
-        lib().nav_adam_multi(descs(*nets), n, parr(*grads), parr(*[o.m for o in opts]),
-                             parr(*[o.v for o in opts]), opts[0].b1, opts[0].b2, opts[0].eps,
-                             (C.c_float * n)(*[c[0] for c in coeffs]),
-                             (C.c_float * n)(*[c[1] for c in coeffs]), float(grad_div), s)
-
-    def _bwd(self, nets, M, dy, ld_dy, masks, s, inp=None, ld_in=0, in_col=0, h_top=None,
-             dz=None, save_mask=0, dx=None, eslab=None):
-        net = nets[0]
-        n = len(nets)
-        with prof.region("mlp_bwd", n * prof.mlp_bwd_flops(net.d_in, net.d_out, net.hidden,
-                                                             net.n_hidden, M, dx is not None,
-                                                             eslab is not None,
-                                                             h_top is not None)):
-            nil = [None] * n
-            lib().nav_mlp_backward(descs(*nets), n, M, parr(*dy), ld_dy, parr(*masks), ptr(inp),
-                                   ld_in, in_col, parr(*(h_top or nil)), parr(*(dz or nil)),
-                                   save_mask, parr(*(dx or nil)), parr(*(eslab or nil)), s)
-
-    # ---- the per-epoch launches with their constant arguments built once (the small-batch
-    # learner of config 1 is bound by the host's issue of ~450 launches per td3_update)
-    def _fast(self):
-        return prof._active is None and self.row_backward
-
-    def _static_key(self):
-        c = self.cfg
-        return (c.batch_size, self.seed, c.policy_noise, c.noise_clip, c.max_action, c.gamma,
-                c.tau, self.split_twins)
+    def _group(self, nets, opts, inp, acts, dz, dy, ld_dy, masks, eslabs, grads, hslabs, splits,
+               bucket, poly):
+        """One net group's (the critic twins', the actor's) weight-gradient, reduce and Adam
+        launches: (work, constant arguments) each."""
+        n, net, B = len(nets), nets[0], self._B
+        g = {"opts": opts, "floats": C.c_float * n, "bucket": bucket, "poly": poly, "wgrad": None}
+        if net.n_hidden > 1:
+            # k_wgrad_fact (d_out 1, 2 hidden layers, whole 64-wide tiles: 2 fp16 products per
+            # f32 product) is timed apart from k_wgrad (3 products): their rooflines differ
+            fact = net.d_out == 1 and net.n_hidden == 2 and net.hp % 64 == 0
+            g["wgrad"] = ("mlp_wgrad_fact" if fact else "mlp_wgrad",
+                          n * prof.mlp_wgrad_flops(net.hidden, net.n_hidden, B),
+                          (descs(*nets), n, B, ptr(inp), 8, 0, parr(*acts), parr(*dz), parr(*dy),
+                           ld_dy, parr(*masks), parr(*hslabs), splits))
+        red = (descs(*nets), n, parr(*hslabs), splits, parr(*eslabs), self.nblk, parr(*grads))
+        adam = (parr(*[o.m for o in opts]), parr(*[o.v for o in opts]), opts[0].b1, opts[0].b2,
+                opts[0].eps)
+        g["red"] = (self._reduce_bytes(nets, eslabs, splits, False), red)
+        g["red_adam"] = (self._reduce_bytes(nets, eslabs, splits, True), red + adam)
+        g["adam"] = (descs(*nets), n, parr(*grads)) + adam
+        return g
 
     def _static(self):
-        key = self._static_key()
-        if self._st is not None and self._st_key == key:
-            return self._st
         c = self.cfg
         B = c.batch_size
+        if B != self._B:
+            self._workspace(B)
+        key = (B, self.seed, c.policy_noise, c.noise_clip, c.max_action, c.gamma, c.tau,
+               self.split_twins)
+        if self._st is not None and self._st_key == key:
+            return self._st
         c1, c2, a = self.critic_network_1, self.critic_network_2, self.actor_network
+        t1, t2 = self.target_critic_network_1, self.target_critic_network_2
         ta, ca = self.target_actor.desc(), a.desc()
         c1d = c1.desc()
         mid, mida = c1.middle_layers(), a.middle_layers()
-        oc, oa = (self.critic_optimizer_1, self.critic_optimizer_2), self.actor_optimizer
-        seed = (self.seed & 0xFFFFFFFF, (self.seed >> 32) & 0xFFFFFFFF)
+        h, nh = c1.hidden, c1.n_hidden
+        fwd, bwd = prof.mlp_fwd_flops, prof.mlp_bwd_flops
+        poly = (descs(self.target_actor), descs(t1, t2), descs(c1, c2), 2, c.tau)
         st = {
             "keep": (ta, ca, c1d),
-            "seed": seed,
-            "cr_head": (C.byref(ta), descs(self.target_critic_network_1,
-                                           self.target_critic_network_2), descs(c1, c2)),
+            "seed": (self.seed & 0xFFFFFFFF, (self.seed >> 32) & 0xFFFFFFFF),
+            "cr_work": (fwd(2, 2, h, nh, B) + 4 * fwd(4, 1, h, nh, B) +
+                        2 * bwd(4, 1, h, nh, B, False, True)),
+            "cr_head": (C.byref(ta), descs(t1, t2), descs(c1, c2)),
             "cr_tail": (c.policy_noise, c.noise_clip, c.max_action, c.gamma, ptr(self.batch),
                         parr(self.dq1, self.dq2), parr(self.loss_part[0], self.loss_part[1]),
                         parr(self.eslab1, self.eslab2), parr(self.acts1, self.acts2), mid,
                         parr(self.mask1, self.mask2), 1, parr(self.dz1, self.dz2), mid,
                         self.split_twins),
+            "ar_work": (fwd(2, 2, h, nh, B) + fwd(4, 1, h, nh, B) + bwd(4, 1, h, nh, B, True) +
+                        bwd(2, 2, h, nh, B, False, True, True)),
             "ar_head": (C.byref(ca), C.byref(c1d)),
             "ar_tail": (ptr(self.batch2), ptr(self.q1), ptr(self.da), ptr(self.acts_a), mida,
                         ptr(self.dz_a), mida, ptr(self.mask_a), ptr(self.mask1),
                         ptr(self.eslab_a)),
+            "c": self._group([c1, c2], (self.critic_optimizer_1, self.critic_optimizer_2),
+                             self.batch, [self.acts1, self.acts2], [self.dz1, self.dz2],
+                             [self.dq1, self.dq2], 1, [self.mask1, self.mask2],
+                             [self.eslab1, self.eslab2], [self.grad_c1, self.grad_c2],
+                             [self.hslab, self.hslab2], self.splits_c, self.grad_c, poly),
+            "a": self._group([a], (self.actor_optimizer,), self.batch2, [self.acts_a],
+                             [self.dz_a], [self.da], 2, [self.mask_a], [self.eslab_a],
+                             [self.grad_a], [self.hslab], self.splits_a, self.grad_a, poly),
         }
-        wc = self._critic_wgrad_args()
-        st["wg_c"] = (descs(c1, c2), 2, B, ptr(wc[0]), wc[1], wc[2], parr(*wc[3]), parr(*wc[4]),
-                      parr(*wc[5]), wc[6], parr(*wc[7]), parr(self.hslab, self.hslab2),
-                      self.splits_c)
-        wa = self._actor_wgrad_args()
-        st["wg_a"] = (descs(a), 1, B, ptr(wa[0]), wa[1], wa[2], parr(*wa[3]), parr(*wa[4]),
-                      parr(*wa[5]), wa[6], parr(*wa[7]), parr(self.hslab), self.splits_a)
-        st["red_c"] = (descs(c1, c2), 2, parr(self.hslab, self.hslab2), self.splits_c,
-                       parr(self.eslab1, self.eslab2), self.nblk, parr(self.grad_c1, self.grad_c2),
-                       parr(*[o.m for o in oc]), parr(*[o.v for o in oc]), oc[0].b1, oc[0].b2,
-                       oc[0].eps)
-        st["red_a"] = (descs(a), 1, parr(self.hslab), self.splits_a, parr(self.eslab_a),
-                       self.nblk, parr(self.grad_a), parr(oa.m), parr(oa.v), oa.b1, oa.b2, oa.eps)
-        st["poly"] = (descs(self.target_actor),
-                      descs(self.target_critic_network_1, self.target_critic_network_2),
-                      descs(c1, c2), 2, c.tau)
-        # shared policy (grad_hook): reduce into the flat bucket, the hook's collective, then the
-        # multi-net Adam on bucket / world_size and (policy epoch) the three soft updates
-        st["redm_c"] = (descs(c1, c2), 2, parr(self.hslab, self.hslab2), self.splits_c,
-                        parr(self.eslab1, self.eslab2), self.nblk, parr(self.grad_c1, self.grad_c2))
-        st["adam_c"] = (descs(c1, c2), 2, parr(self.grad_c1, self.grad_c2),
-                        parr(*[o.m for o in oc]), parr(*[o.v for o in oc]), oc[0].b1, oc[0].b2,
-                        oc[0].eps)
-        st["redm_a"] = (descs(a), 1, parr(self.hslab), self.splits_a, parr(self.eslab_a),
-                        self.nblk, parr(self.grad_a))
-        st["adam_a"] = (descs(a), 1, parr(self.grad_a), parr(oa.m), parr(oa.v), oa.b1, oa.b2,
-                        oa.eps)
-
-        st["wgrad"] = c1.n_hidden > 1
         self._st, self._st_key = st, key
         return st
 
@@ -294,6 +223,34 @@ class TD3:
             d = replay.desc()
             self._rd = (replay, (d, C.byref(d)))
         return self._rd[1][1]
+
+    def _wgrad(self, g, s):
+        """Hidden x hidden weight gradients of the group's 1-2 same-shape nets: one MFMA launch
+        writing `splits` partial slabs per net."""
+        if g["wgrad"] is not None:
+            name, work, args = g["wgrad"]
+            self._run(name, work, lib().nav_mlp_wgrad, *args, s)
+
+    def _reduce(self, g, s):
+        """Fixed-order reduce of the weight-gradient slabs and the fwd/bwd edge partials into the
+        group's flat gradients, no Adam."""
+        work, args = g["red"]
+        self._run("grad_reduce", work, lib().nav_grad_reduce_multi, *args, s)
+
+    @staticmethod
+    def _coeffs(g):
+        """The group's next Adam steps: (step sizes, sqrt(1 - b2^t)) as float arrays."""
+        ss, bc = zip(*[o.advance() for o in g["opts"]])
+        return g["floats"](*ss), g["floats"](*bc)
+
+    def _adam(self, g, s, grad_div=1.0, soft_update=False):
+        """One multi-net Adam launch on flat gradients (already reduced) / grad_div; with
+        soft_update the three soft updates in the same launch."""
+        ss, bc = self._coeffs(g)
+        if soft_update:
+            lib().nav_adam_polyak_multi(*g["adam"], ss, bc, float(grad_div), *g["poly"], s)
+        else:
+            lib().nav_adam_multi(*g["adam"], ss, bc, float(grad_div), s)
 
     def _hook(self, bucket, stream):
         # the collective runs on torch's current stream: make it the launch stream, so it starts
@@ -305,123 +262,60 @@ class TD3:
         # collective's stream waits for it and it for the collective), when a timer asks
         nbytes = bucket.numel() * bucket.element_size()
         if stream is None:
-            with prof.region("allreduce", nbytes):
-                self.grad_hook(bucket)
+            self._run("allreduce", nbytes, self.grad_hook, bucket)
         else:
             with torch.cuda.stream(stream):
-                with prof.region("allreduce", nbytes):
-                    self.grad_hook(bucket)
+                self._run("allreduce", nbytes, self.grad_hook, bucket)
 
-    def _critic_epoch_fast(self, replay, idx, eps, s, stream):
-        c = self.cfg
-        B = c.batch_size
-        self._workspace(B)
-        st, L = self._static(), lib()
-        L.nav_td3_critic_rows(*st["cr_head"], self._replay_ref(replay), len(replay), B,
-                              None if idx is None else C.c_void_p(idx.data_ptr()), *st["seed"],
-                              self.update_counter,
-                              None if eps is None else C.c_void_p(eps.data_ptr()), *st["cr_tail"],
-                              s)
-        if st["wgrad"]:
-            L.nav_mlp_wgrad(*st["wg_c"], s)
-        o1, o2 = self.critic_optimizer_1.advance(), self.critic_optimizer_2.advance()
-        ss, bc = (C.c_float * 2)(o1[0], o2[0]), (C.c_float * 2)(o1[1], o2[1])
-        if self.grad_hook is None:
-            L.nav_grad_reduce_adam(*st["red_c"], ss, bc, s)
-            return
-        L.nav_grad_reduce_multi(*st["redm_c"], s)
-        self._hook(self.grad_c, stream)
-        L.nav_adam_multi(*st["adam_c"], ss, bc, self.grad_div, s)
-
-    def _actor_epoch_fast(self, replay, idx, s, stream, soft_update):
-        c = self.cfg
-        B = c.batch_size
-        self._workspace(B)
-        st, L = self._static(), lib()
-        L.nav_td3_actor_rows(*st["ar_head"], self._replay_ref(replay), len(replay), B,
-                             None if idx is None else C.c_void_p(idx.data_ptr()), *st["seed"],
-                             self.update_counter, *st["ar_tail"], s)
-        if st["wgrad"]:
-            L.nav_mlp_wgrad(*st["wg_a"], s)
-        o = self.actor_optimizer.advance()
-        ss, bc = (C.c_float * 1)(o[0]), (C.c_float * 1)(o[1])
+    def _step(self, g, s, stream, soft_update=False):
+        """After a rows launch: the weight gradients, then the fixed-order reduce of those and
+        the fwd/bwd edge partials fused with each net's Adam step (robot.py:236-239) of 1-2 nets
+        (and on a policy epoch the three soft updates). With a grad_hook (shared policy) the
+        reduce writes the flat gradient bucket without Adam, the hook all-reduces it, and one
+        multi-net Adam launch applies bucket / world_size (and the soft updates)."""
+        self._wgrad(g, s)
         if self.grad_hook is not None:
-            L.nav_grad_reduce_multi(*st["redm_a"], s)
-            self._hook(self.grad_a, stream)
-            if soft_update:  # the actor's step and the three soft updates in one launch
-                L.nav_adam_polyak_multi(*st["adam_a"], ss, bc, self.grad_div, *st["poly"], s)
-            else:
-                L.nav_adam_multi(*st["adam_a"], ss, bc, self.grad_div, s)
-        elif soft_update:
-            L.nav_grad_reduce_adam_polyak(*st["red_a"], ss, bc, *st["poly"], s)
+            self._reduce(g, s)
+            self._hook(g["bucket"], stream)
+            self._adam(g, s, self.grad_div, soft_update)
+            return
+        work, args = g["red_adam"]
+        ss, bc = self._coeffs(g)
+        if soft_update:  # the actor's step and all three soft updates in one launch
+            self._run("grad_reduce", work, lib().nav_grad_reduce_adam_polyak, *args, ss, bc,
+                      *g["poly"], s)
         else:
-            L.nav_grad_reduce_adam(*st["red_a"], ss, bc, s)
+            self._run("grad_reduce", work, lib().nav_grad_reduce_adam, *args, ss, bc, s)
 
     # robot.py:312-366
     def _critic_rows(self, replay, idx, eps, s):
-        c = self.cfg
-        B = c.batch_size
-        self._workspace(B)
-        c1, c2 = self.critic_network_1, self.critic_network_2
-        mid = c1.middle_layers()
-        rd = replay.desc()
         # sample + target actor with smoothing noise + twin target critics + TD target + online
         # twin forward with the MSE gradient + each online critic's row backward: one launch,
         # rows in LDS throughout
-        h, nh = c1.hidden, c1.n_hidden
-        work = (prof.mlp_fwd_flops(2, 2, h, nh, B) + 4 * prof.mlp_fwd_flops(4, 1, h, nh, B) +
-                2 * prof.mlp_bwd_flops(4, 1, h, nh, B, False, True))
-        with prof.region("critic_rows", work):
-            lib().nav_td3_critic_rows(
-                C.byref(self.target_actor.desc()),
-                descs(self.target_critic_network_1, self.target_critic_network_2),
-                descs(c1, c2), C.byref(rd), len(replay), B, ptr(idx),
-                self.seed & 0xFFFFFFFF, (self.seed >> 32) & 0xFFFFFFFF, self.update_counter,
-                ptr(eps), c.policy_noise, c.noise_clip, c.max_action, c.gamma, ptr(self.batch),
-                parr(self.dq1, self.dq2), parr(self.loss_part[0], self.loss_part[1]),
-                parr(self.eslab1, self.eslab2), parr(self.acts1, self.acts2), mid,
-                parr(self.mask1, self.mask2), int(self.row_backward), parr(self.dz1, self.dz2),
-                mid, self.split_twins, s)
-        if not self.row_backward:  # separate backward launch (A/B of the fusion)
-            self._bwd([c1, c2], B, [self.dq1, self.dq2], 1, [self.mask1, self.mask2], s,
-                      inp=self.batch, ld_in=8, in_col=0, dz=[self.dz1, self.dz2], save_mask=mid,
-                      eslab=[self.eslab1, self.eslab2])
-
-    def _critic_wgrad_args(self):
-        return (self.batch, 8, 0, [self.acts1, self.acts2], [self.dz1, self.dz2],
-                [self.dq1, self.dq2], 1, [self.mask1, self.mask2])
+        st = self._static()
+        self._run("critic_rows", st["cr_work"], lib().nav_td3_critic_rows, *st["cr_head"],
+                  self._replay_ref(replay), len(replay), self._B, ptr(idx), *st["seed"],
+                  self.update_counter, ptr(eps), *st["cr_tail"], s)
+        return st["c"]
 
     def train_critic(self, replay, idx=None, eps=None, stream=None):
         s = stream_handle(stream)
-        if self._fast():
-            return self._critic_epoch_fast(replay, idx, eps, s, stream)
-        self._critic_rows(replay, idx, eps, s)
-        c1, c2 = self.critic_network_1, self.critic_network_2
-        B = self.cfg.batch_size
         # both critics' weight gradients, then reduce + Adam: one launch each
-        self._grads_and_step([c1, c2], [self.critic_optimizer_1, self.critic_optimizer_2], B,
-                             *self._critic_wgrad_args(), [self.eslab1, self.eslab2],
-                             [self.grad_c1, self.grad_c2], [self.hslab, self.hslab2], s, stream)
+        self._step(self._critic_rows(replay, idx, eps, s), s, stream)
 
     def critic_gradients(self, replay, idx=None, eps=None, stream=None):
         """train_critic's gradient phase alone: both critics' flat gradients into the `grad_c`
         bucket ([critic 1 | critic 2], contiguous), no parameter changes. With critic_step this
         is train_critic's shared-policy path split where the collective goes."""
         s = stream_handle(stream)
-        self._critic_rows(replay, idx, eps, s)
-        c1, c2 = self.critic_network_1, self.critic_network_2
-        splits = self._wgrad([c1, c2], self.cfg.batch_size, *self._critic_wgrad_args(),
-                             [self.hslab, self.hslab2], s)
-        lib().nav_grad_reduce_multi(descs(c1, c2), 2, parr(self.hslab, self.hslab2), splits,
-                                    parr(self.eslab1, self.eslab2), self.nblk,
-                                    parr(self.grad_c1, self.grad_c2), s)
+        g = self._critic_rows(replay, idx, eps, s)
+        self._wgrad(g, s)
+        self._reduce(g, s)
         return self.grad_c
 
     def critic_step(self, grad_div=1.0, stream=None):
         """Adam on both critics from the `grad_c` bucket / grad_div (one launch)."""
-        self._adam([self.critic_network_1, self.critic_network_2],
-                   [self.critic_optimizer_1, self.critic_optimizer_2],
-                   [self.grad_c1, self.grad_c2], stream_handle(stream), grad_div)
+        self._adam(self._static()["c"], stream_handle(stream), grad_div)
 
     def critic_loss_values(self):
         """(loss1, loss2) of the last train_critic (mean squared TD error), synchronising."""
@@ -430,54 +324,30 @@ class TD3:
 
     # robot.py:369-398
     def _actor_rows(self, replay, idx, s):
-        c = self.cfg
-        B = c.batch_size
-        self._workspace(B)
-        net = self.actor_network
-        c1 = self.critic_network_1
-        rd = replay.desc()
-        h, nh = net.hidden, net.n_hidden
         # sample + actor forward + critic-1 forward + backward of -mean(Q) to the action + the
         # actor's row backward with its edge partials: one launch
-        work = (prof.mlp_fwd_flops(2, 2, h, nh, B) + prof.mlp_fwd_flops(4, 1, h, nh, B) +
-                prof.mlp_bwd_flops(4, 1, h, nh, B, True) +
-                prof.mlp_bwd_flops(2, 2, h, nh, B, False, True, True))
-        with prof.region("actor_rows", work):
-            lib().nav_td3_actor_rows(
-                C.byref(net.desc()), C.byref(c1.desc()), C.byref(rd), len(replay), B, ptr(idx),
-                self.seed & 0xFFFFFFFF, (self.seed >> 32) & 0xFFFFFFFF, self.update_counter,
-                ptr(self.batch2), ptr(self.q1), ptr(self.da), ptr(self.acts_a),
-                net.middle_layers(), ptr(self.dz_a), net.middle_layers(),
-                ptr(self.mask_a), ptr(self.mask1), ptr(self.eslab_a), s)
-
-    def _actor_wgrad_args(self):
-        return (self.batch2, 8, 0, [self.acts_a], [self.dz_a], [self.da], 2, [self.mask_a])
+        st = self._static()
+        self._run("actor_rows", st["ar_work"], lib().nav_td3_actor_rows, *st["ar_head"],
+                  self._replay_ref(replay), len(replay), self._B, ptr(idx), *st["seed"],
+                  self.update_counter, *st["ar_tail"], s)
+        return st["a"]
 
     def train_actor(self, replay, idx=None, stream=None, soft_update=False):
         """robot.py:369-398; with soft_update the three soft updates of robot.py:283-285 that
         follow it on a policy epoch ride in the actor's reduce + Adam launch."""
         s = stream_handle(stream)
-        if self._fast():
-            return self._actor_epoch_fast(replay, idx, s, stream, soft_update)
-        self._actor_rows(replay, idx, s)
-        self._grads_and_step([self.actor_network], [self.actor_optimizer], self.cfg.batch_size,
-                             *self._actor_wgrad_args(), [self.eslab_a], [self.grad_a],
-                             [self.hslab], s, stream, soft_update=soft_update)
+        self._step(self._actor_rows(replay, idx, s), s, stream, soft_update)
 
     def actor_gradients(self, replay, idx=None, stream=None):
         """train_actor's gradient phase alone: the actor's flat gradient into `grad_a`."""
         s = stream_handle(stream)
-        self._actor_rows(replay, idx, s)
-        net = self.actor_network
-        splits = self._wgrad([net], self.cfg.batch_size, *self._actor_wgrad_args(),
-                             [self.hslab], s)
-        lib().nav_grad_reduce_multi(descs(net), 1, parr(self.hslab), splits,
-                                    parr(self.eslab_a), self.nblk, parr(self.grad_a), s)
+        g = self._actor_rows(replay, idx, s)
+        self._wgrad(g, s)
+        self._reduce(g, s)
         return self.grad_a
 
     def actor_step(self, grad_div=1.0, stream=None):
-        self._adam([self.actor_network], [self.actor_optimizer], [self.grad_a],
-                   stream_handle(stream), grad_div)
+        self._adam(self._static()["a"], stream_handle(stream), grad_div)
 
     def actor_loss_value(self):
         return -(self.q1.sum() / self._B).item()
@@ -524,12 +394,11 @@ class TD3:
             if track_losses:
                 self.critic_losses.append(sum(self.critic_loss_values()) / 2)
             if epoch % self.cfg.policy_update_delay == 0:
+                # the three soft updates ride in the actor's reduce + Adam launch
                 self.train_actor(replay, idx=idx_fn() if idx_fn else None, stream=stream,
-                                 soft_update=self.fuse_soft_update)
+                                 soft_update=True)
                 if track_losses:
                     self.actor_losses.append(self.actor_loss_value())
-                if not self.fuse_soft_update:
-                    self.soft_update_all(stream)
             self.update_counter += 1
 
     def networks(self):

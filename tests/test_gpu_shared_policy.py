@@ -133,8 +133,8 @@ def _call_plan(B, epochs, seed):
 
 @pytest.mark.parametrize("hidden,nh,B,epochs", [(256, 2, 8192, 4), (200, 3, 1000, 3)])
 def test_grad_hook_branch_gradient_level(hidden, nh, B, epochs):
-    """The product shared-policy branch (TD3._grads_and_step with a grad_hook: reduce ->
-    hook -> nav_adam_multi(grad_div), robot.py:355-363, 393-395), driven through td3_update /
+    """The product shared-policy branch (TD3._step with a grad_hook: reduce -> hook ->
+    nav_adam_multi(grad_div), robot.py:355-363, 393-395), driven through td3_update /
     train_critic / train_actor by two half-batch learners in two threads, against one full-batch
     learner. Checked BEFORE Adam: the summed bucket / 2 equals the full learner's flat gradient
     (rtol 1e-4; the scale, <g, g_full> / |g_full|^2, within 1e-5 of 1 — a missing or doubled
@@ -303,7 +303,7 @@ def test_adam_multi_grad_div_vs_oracle(grad_div):
 def _rank_worker(rank, ws, port, hidden, nh, B, epochs, q):
     """One rank of the 2-process shared-policy run: the product hook (nav.dist.GradAllReduce:
     one SUM all_reduce per bucket, here over gloo since RCCL refuses two ranks on one device)
-    inside TD3._grads_and_step, driven by td3_update on this rank's half of each batch."""
+    inside TD3._step, driven by td3_update on this rank's half of each batch."""
     import os
     import sys
     import torch.distributed as dist

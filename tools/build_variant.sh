@@ -1,38 +1,28 @@
 #!/bin/bash
-# Build an A/B variant of libnavenv.so with extra -D flags on one translation unit (tuning only):
-#   tools/build_variant.sh NAME learner|env|mlpN "-DFOO=1 ..."  (mlpN: the row kernels of hidden
-#   width 32*N; mlp8 = 256; mlp0 = the row kernels' C-ABI object)
-# -> abl/libnavenv_NAME.so (bind it with python tools/withlib.py abl/libnavenv_NAME.so SCRIPT ...)
-# The learner unit's knobs: -DNAV_WGRAD_FACT_WIDE=0 (k_wgrad_fact as 128 x 64 wave tiles at hp 256
-# instead of 256 x 32), -DNAV_WG_SKEW_FACT=R / -DNAV_WG_SKEW_OPND=R (rows moved to the first wave of
-# a SIMD pair per 256 rows), -DNAV_WGRAD_TRACE (tools/wgrad_trace.py). WIDE=0 as the unit name is
-# short for the first:  tools/build_variant.sh narrow WIDE=0
+# Build an A/B variant of libnavenv.so with extra -D flags on some translation units (tuning
+# only), through the package Makefile's UNIT hook: one flag list, one object list.
+#   tools/build_variant.sh NAME "UNIT ..." "-DFOO=1 ..."
+#   UNIT: learner | env | mlpN (the row kernels of hidden width 32*N; mlp8 = 256) | mlp0 (the row
+#   kernels' C-ABI object; "mlp0 mlp8" rebuilds the dispatch and the 256-wide kernels together) |
+#   mlp8agpr (mlp8 without the scheduler / VGPR-form flags); NOSCHED=1 in the environment drops
+#   those flags from every unit named
+# -> abl/libnavenv_NAME.so, its objects in abl/NAME.build (bind it with
+#    python tools/withlib.py abl/libnavenv_NAME.so SCRIPT ...)
+# The learner unit's knobs: -DNAV_WG_SKEW_FACT=R / -DNAV_WG_SKEW_OPND=R (rows moved to the first
+# wave of a SIMD pair per 256 rows), -DNAV_WGRAD_TRACE (tools/wgrad_trace.py).
 set -eu
-if [ "${2:-}" = "WIDE=0" ]; then set -- "$1" learner "-DNAV_WGRAD_FACT_WIDE=0 ${3:-}"; fi
 cd "$(dirname "$0")/.."
-name=$1; unit=$2; flags=$3
-P=residual-td3-robot-navigation_amd
-B=$P/build
-make -s -C $P
-mkdir -p abl
-FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -Iinclude -I$P/csrc"
-objs="$B/env_kernels.o $B/learner_kernels.o $B/mlp_kernels.o"
-for n in 1 2 3 4 5 6 7 8; do objs="$objs $B/mlp_nt$n.o"; done
-case $unit in
-  learner) sched="-mllvm -amdgpu-sched-strategy=max-ilp"
-           [ -n "${NOSCHED:-}" ] && sched=""  # NOSCHED=1: the default machine scheduler
-           /opt/rocm/bin/hipcc $FL $sched $flags -c $P/csrc/learner_kernels.hip -o abl/$name.o
-           objs=${objs/$B\/learner_kernels.o/abl\/$name.o} ;;
-  env) /opt/rocm/bin/hipcc $FL $flags -c $P/csrc/env_kernels.hip -o abl/$name.o
-       objs=${objs/$B\/env_kernels.o/abl\/$name.o} ;;
-  mlp0) /opt/rocm/bin/hipcc $FL -mllvm -amdgpu-mfma-vgpr-form=1 -mllvm -amdgpu-sched-strategy=max-ilp -fno-slp-vectorize $flags -DNAV_MLP_PART=0 -c $P/csrc/mlp_kernels.hip -o abl/$name.o
-        objs=${objs/$B\/mlp_kernels.o/abl\/$name.o} ;;
-  mlp[1-8]) n=${unit#mlp}
-        /opt/rocm/bin/hipcc $FL -mllvm -amdgpu-mfma-vgpr-form=1 -mllvm -amdgpu-sched-strategy=max-ilp -fno-slp-vectorize $flags -DNAV_MLP_PART=$n -c $P/csrc/mlp_kernels.hip -o abl/$name.o
-        objs=${objs/$B\/mlp_nt$n.o/abl\/$name.o} ;;
-  mlp8agpr) /opt/rocm/bin/hipcc $FL $flags -DNAV_MLP_PART=8 -c $P/csrc/mlp_kernels.hip -o abl/$name.o
-        objs=${objs/$B\/mlp_nt8.o/abl\/$name.o} ;;
-  *) echo "unit?"; exit 2 ;;
-esac
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o abl/libnavenv_$name.so $objs
+name=$1; flags=${3:-}; units=""; plain=${NOSCHED:-}
+for u in $2; do
+  case $u in
+    learner) units="$units learner_kernels" ;;
+    env) units="$units env_kernels" ;;
+    mlp0) units="$units mlp_kernels" ;;
+    mlp[1-8]) units="$units mlp_nt${u#mlp}" ;;
+    mlp8agpr) units="$units mlp_nt8"; plain=1 ;;
+    *) echo "unit?"; exit 2 ;;
+  esac
+done
+make -s -j"${JOBS:-16}" -C residual-td3-robot-navigation_amd BUILD="$PWD/abl/$name.build" \
+  LIB="$PWD/abl/libnavenv_$name.so" UNIT="$units" UNIT_EXTRA="$flags" UNIT_PLAIN="$plain"
 echo abl/libnavenv_$name.so
