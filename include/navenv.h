@@ -536,6 +536,91 @@ int nav_fill(float* x, int64_t n, float value, void* stream);
 int nav_strided_copy(const float* src, int32_t ld_src, int32_t col_src, float* dst, int32_t ld_dst,
                      int32_t col_dst, int64_t rows, int32_t cols, void* stream);
 
+/* ---- Population learner: every member's TD3 epoch (robot.py:258-285) in one launch per kernel ----
+ * One member: everything its four per-epoch calls (nav_td3_critic_rows, nav_td3_actor_rows,
+ * nav_mlp_wgrad, nav_grad_reduce_adam / _polyak) take today. The members share nothing. All
+ * pointers are device memory; the workspace is sized for batch B as the single-member calls
+ * document it (row blocks = nav_mlp_row_blocks(B)). Nullable: idx_critic, idx_actor and eps (the
+ * injected sample indices [B] and smoothing noise [B][2]; NULL = Philox), grad_* (the flat
+ * gradients are then not stored), and for n_hidden <= 2 acts* and dz* (no layer is saved). */
+typedef struct nav_td3_member {
+    nav_mlp actor, critics[2], target_actor, target_critics[2];
+    nav_replay replay;
+    float *m_actor, *v_actor; /* Adam moments [param_count] */
+    float *m_critic[2], *v_critic[2];
+    double actor_lr, critic_lr; /* robot.py:236-239 */
+    float policy_noise, noise_clip, max_action, gamma, tau;
+    uint32_t seed_lo, seed_hi; /* the member's Philox key (sampling, smoothing noise) */
+    const int64_t* idx_critic;
+    const int64_t* idx_actor;
+    const float* eps;
+    float* batch;        /* [B][8] the critic phase's sampled rows */
+    float* batch_actor;  /* [B][8] the actor phase's */
+    float* dq[2];        /* [B] */
+    float* loss_part[2]; /* [row blocks] */
+    float* edge_slabs[2];    /* [row blocks][nav_mlp_edge_count(4, 1, ..)] */
+    float* edge_slabs_actor; /* [row blocks][nav_mlp_edge_count(2, 2, ..)] */
+    float* acts[2];          /* [n_hidden][B][hidden_pad] */
+    float* acts_actor;
+    float* dz[2];
+    float* dz_actor;
+    uint16_t* masks[2];      /* nav_mlp_mask_count words */
+    uint16_t* masks_actor;
+    float* q;                /* [B] Q1(s, pi(s)), nullable */
+    float* da;               /* [B][2] */
+    float* hidden_slabs[2];  /* [max splits][nav_mlp_hidden_count]; the actor uses hidden_slabs[0] */
+    float* grad_critic[2];   /* [param_count], nullable */
+    float* grad_actor;
+} nav_td3_member;
+/* `members` is a host array [n_members]; `table` is device memory of
+ * nav_td3_pop_table_bytes(n_members) bytes that nav_td3_pop_table_build fills on the stream with
+ * every member's kernel arguments for batch B and the given weight-gradient split counts, as
+ * nav_pop_table_build does for the tick: once per population, and again only when a pointer, a
+ * hyper-parameter, B or a split count changes (the weights, moments and rings change in place
+ * without a rebuild). What changes per launch and is common to all members travels by value: the
+ * replay fill `size` (the rings have one capacity and advance together), the Philox `counter`,
+ * and Adam's betas, eps and bias corrections; so steady-state training copies nothing to the
+ * device. Every entry point checks on the host, before any HIP call (NAV_EINVAL): n_members in
+ * 1 .. 256, B >= 1, one network shape across members, equal ring capacities, 1 <= size <=
+ * capacity, splits >= 1, group in {0, 1}, and every pointer (and save-mask rule) that the
+ * single-member entry point refuses. The launches take the host array for the check and the
+ * launch shape only; a table built from other arrays is the caller's error. */
+int64_t nav_td3_pop_table_bytes(int32_t n_members);
+int nav_td3_pop_table_build(const nav_td3_member* members, int32_t n_members, int64_t B,
+                            int32_t splits_critic, int32_t splits_actor, void* table,
+                            void* stream);
+/* nav_td3_critic_rows (robot.py:329-361, row_backward on, the middle layers saved) of every member
+ * in one launch: grid (row blocks, twins, members), member m's workgroups read its arguments from
+ * the table. split_twins < 0: the library's choice from all members' rows (split for n_members * B
+ * <= 2048); the results are bit-identical either way, and equal to member m's own
+ * nav_td3_critic_rows with the same size and counter. No L2 warmer rows. */
+int nav_td3_critic_rows_pop(const nav_td3_member* members, int32_t n_members, int64_t B,
+                            const void* table, int64_t size, uint32_t counter,
+                            int32_t split_twins, void* stream);
+/* nav_td3_actor_rows (robot.py:382-390) of every member in one launch. */
+int nav_td3_actor_rows_pop(const nav_td3_member* members, int32_t n_members, int64_t B,
+                           const void* table, int64_t size, uint32_t counter, void* stream);
+/* The split count that fills the chip with all members' tile jobs: 256 / (jobs * n_members), at
+ * most one split per 512 rows and at least 1; n_members = 1 gives nav_mlp_wgrad_splits. */
+int32_t nav_mlp_wgrad_splits_pop(int32_t n_members, int32_t n_nets, int32_t d_out,
+                                 int32_t hidden_pad, int32_t n_hidden, int64_t M);
+/* nav_mlp_wgrad of every member in one launch after its rows launch (autograd of
+ * robot.py:355-363 / 388-395): group 0 = the twin critics (from batch, dq), group 1 = the actor
+ * (from batch_actor, da); `splits` is the group's count the table was built with. Launches
+ * nothing for n_hidden == 1. */
+int nav_mlp_wgrad_pop(const nav_td3_member* members, int32_t n_members, int64_t B,
+                      const void* table, int32_t group, int32_t splits, void* stream);
+/* nav_grad_reduce_adam of every member's group in one launch (robot.py:236-239), then the packed
+ * images of what it wrote in one more. bc1 = 1 - beta1^t and bc2_sqrt = sqrt(1 - beta2^t) of the
+ * common step t; member m's step size is formed on the device as (float)(lr_m / bc1), the two
+ * roundings of the host's lr / (1 - b1^t) passed as a float. soft_update != 0 (group 1 only):
+ * also the member's three soft updates with its tau (robot.py:283-285), as
+ * nav_grad_reduce_adam_polyak. */
+int nav_grad_reduce_adam_pop(const nav_td3_member* members, int32_t n_members, int64_t B,
+                             const void* table, int32_t group, float beta1, float beta2,
+                             float eps, double bc1, float bc2_sqrt, int32_t soft_update,
+                             void* stream);
+
 /* ---- kernel timing (measurement only, not on the reference's interface) ----
  * Timing events recorded with a device-scope release (hipEventReleaseToDevice): bracketing a
  * launch costs no system-scope L2 writeback, so timing the bench's timed region does not stretch

@@ -1033,6 +1033,7 @@ NAV_DEV void wgrad_tile(const WgradArgs& a, const TileJob& t, float* smem) {
 
 // grid: nets x tile jobs x splits workgroups of 8 waves (one kernel per path: each gets its own
 // register allocation)
+#ifndef NAV_LEARNER_POP
 __global__ __launch_bounds__(WG_THREADS) void k_wgrad(WgradArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     wgrad_tile<false>(a, wgrad_job(a, blockIdx.x, gridDim.x), smem);
@@ -1047,6 +1048,7 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad_fact(WgradArgs a) {
     __shared__ uint4 tab[256];
     wgrad_tile_fact<NI, D, KH>(a, wgrad_job(a, blockIdx.x, gridDim.x), smem, tab);
 }
+#endif  // !NAV_LEARNER_POP
 
 // ---------------- optimizer / target update, refreshing the packed images ----------------
 struct PackInfo {
@@ -1075,65 +1077,13 @@ struct PackArgs {
     int n, per_net, cg;
 };
 
+// (the statements are pack_img_body.inc, once per form: the plain kernel's machine code is
+// pinned, and reaching `a` through a shared device function changed its register allocation)
+#ifndef NAV_LEARNER_POP
 __global__ __launch_bounds__(kBlock) void k_pack_img(PackArgs a) {
-    __shared__ float cmax[16][16];
-    int b = blockIdx.x;
-    const int jn = b / a.per_net;
-    b -= jn * a.per_net;
-    const PackJob& J = a.j[jn];
-    const int hp = J.pk.hp;
-    const int g = b % a.cg;
-    b /= a.cg;
-    const int which = b & 1, L = (b >> 1) + 1;
-    if (L >= J.pk.n_hidden || g * 16 >= hp) return;  // workgroup-uniform
-    const float* W = J.p + J.pk.w_off[L];
-    float* img = J.pk.packed + (int64_t)(L - 1) * 2 * split_image_floats(hp) +
-                 which * split_image_floats(hp);
-    const int c = threadIdx.x & 15, kq = threadIdx.x >> 4;
-    const int n = g * 16 + c, k0 = 16 * kq;
-    const bool on = k0 < hp;  // hp is a multiple of 32 (and n < hp: whole 16-column groups)
-    float v[16];
-    float m = 0.f;
-    if (on) {
-        if (which == 0) {
-            const float4* r = reinterpret_cast<const float4*>(W + (int64_t)n * hp + k0);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 u = r[q];
-                v[4 * q] = u.x; v[4 * q + 1] = u.y; v[4 * q + 2] = u.z; v[4 * q + 3] = u.w;
-            }
-        } else {
-#pragma unroll
-            for (int t = 0; t < 16; ++t) v[t] = W[(int64_t)(k0 + t) * hp + n];
-            if (J.pk.d_out == 1 && L == J.pk.n_hidden - 1) {  // workgroup-uniform
-                const float* Wo = J.p + J.pk.w_off[J.pk.n_hidden];
-#pragma unroll
-                for (int t = 0; t < 16; ++t) v[t] = Wo[k0 + t] * v[t];
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < 16; ++t) m = fmaxf(m, fabsf(v[t]));
-    }
-    cmax[kq][c] = m;
-    __syncthreads();
-    if (!on) return;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) m = fmaxf(m, cmax[q][c]);
-    const int e = pow2_exp(m);
-    const float sc = ldexpf(1.f, e);
-    _Float16* h16 = reinterpret_cast<_Float16*>(img);
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        float xs[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) xs[t] = v[8 * half + t] * sc;
-        const Split2 sp = split2_8(xs);
-        const int k = k0 + 8 * half;
-        *reinterpret_cast<f16x8*>(h16 + split_entry(hp, 0, k, n)) = sp.h;
-        *reinterpret_cast<f16x8*>(h16 + split_entry(hp, 1, k, n)) = sp.l;
-    }
-    if (kq == 0) reinterpret_cast<int*>(img + (int64_t)hp * hp)[n] = e;
+#include "pack_img_body.inc"
 }
+#endif
 
 NAV_DEV float adam1(float& p, float g, float& m, float& v, float b1w, float b2, float omb2,
                     float eps, float step_size, float bc2s) {
@@ -1192,12 +1142,26 @@ struct RedArgs {
 
 // Adam on the float4 of parameters at flat4 with its finished gradient g and the net's own
 // target (when soft-updated in the launch); the packed images follow in k_pack_img
-NAV_DEV void adam_out(const RedArgs& a, const RedNet& rn, int64_t flat4, float4 g) {
+// (POP, the population form: Adam's constants, the step's step size and sqrt(1 - b2^t) come with
+// the launch, `st`, instead of the table entry, which then holds none of them)
+struct AdamStep {
+    float step_size, bc2s, b1w, b2, omb2, eps;
+};
+template <bool POP>
+NAV_DEV void adam_out(const RedArgs& a, const RedNet& rn, int64_t flat4, float4 g,
+                      const AdamStep& st) {
     float4 pp = rn.p[flat4], mm = rn.m[flat4], vv = rn.v[flat4];
-    adam1(pp.x, g.x, mm.x, vv.x, a.b1w, a.b2, a.omb2, a.eps, rn.step_size, rn.bc2s);
-    adam1(pp.y, g.y, mm.y, vv.y, a.b1w, a.b2, a.omb2, a.eps, rn.step_size, rn.bc2s);
-    adam1(pp.z, g.z, mm.z, vv.z, a.b1w, a.b2, a.omb2, a.eps, rn.step_size, rn.bc2s);
-    adam1(pp.w, g.w, mm.w, vv.w, a.b1w, a.b2, a.omb2, a.eps, rn.step_size, rn.bc2s);
+    if constexpr (POP) {
+        adam1(pp.x, g.x, mm.x, vv.x, st.b1w, st.b2, st.omb2, st.eps, st.step_size, st.bc2s);
+        adam1(pp.y, g.y, mm.y, vv.y, st.b1w, st.b2, st.omb2, st.eps, st.step_size, st.bc2s);
+        adam1(pp.z, g.z, mm.z, vv.z, st.b1w, st.b2, st.omb2, st.eps, st.step_size, st.bc2s);
+        adam1(pp.w, g.w, mm.w, vv.w, st.b1w, st.b2, st.omb2, st.eps, st.step_size, st.bc2s);
+    } else {
+        adam1(pp.x, g.x, mm.x, vv.x, a.b1w, a.b2, a.omb2, a.eps, rn.step_size, rn.bc2s);
+        adam1(pp.y, g.y, mm.y, vv.y, a.b1w, a.b2, a.omb2, a.eps, rn.step_size, rn.bc2s);
+        adam1(pp.z, g.z, mm.z, vv.z, a.b1w, a.b2, a.omb2, a.eps, rn.step_size, rn.bc2s);
+        adam1(pp.w, g.w, mm.w, vv.w, a.b1w, a.b2, a.omb2, a.eps, rn.step_size, rn.bc2s);
+    }
     rn.p[flat4] = pp;
     rn.m[flat4] = mm;
     rn.v[flat4] = vv;
@@ -1211,10 +1175,11 @@ NAV_DEV void adam_out(const RedArgs& a, const RedNet& rn, int64_t flat4, float4 
     }
 }
 
-template <bool ADAM>
-NAV_DEV void red_out(const RedArgs& a, const RedNet& rn, int64_t flat4, float4 g) {
+template <bool ADAM, bool POP>
+NAV_DEV void red_out(const RedArgs& a, const RedNet& rn, int64_t flat4, float4 g,
+                     const AdamStep& st) {
     if (rn.grad) rn.grad[flat4] = g;
-    if (ADAM) adam_out(a, rn, flat4, g);
+    if (ADAM) adam_out<POP>(a, rn, flat4, g, st);
 }
 
 // soft update of element i of the pairs' concatenation (k_polyak_multi's body)
@@ -1233,8 +1198,8 @@ NAV_DEV void polyak_elem(const PolyArgs& a, int64_t i) {
     q.t[j] = t;
 }
 
-template <bool ADAM>
-__global__ __launch_bounds__(kBlock) void k_grad_reduce(RedArgs a) {
+template <bool ADAM, bool POP>
+NAV_DEV void grad_reduce_body(const RedArgs& a, const AdamStep& st) {
     __shared__ float4 part[4][64];
     const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
     int b = blockIdx.x;
@@ -1269,7 +1234,7 @@ __global__ __launch_bounds__(kBlock) void k_grad_reduce(RedArgs a) {
         }
         const int64_t per = (int64_t)net.hp * net.hp / 4;
         const int L = (int)(i / per) + 1;
-        red_out<ADAM>(a, rn, net.w_off[L] / 4 + i % per, r);
+        red_out<ADAM, POP>(a, rn, net.w_off[L] / 4 + i % per, r, st);
         return;
     }
     // edge entries: one block = 16 float4 columns x 16 groups of edge blocks; thread (column
@@ -1309,7 +1274,12 @@ __global__ __launch_bounds__(kBlock) void k_grad_reduce(RedArgs a) {
         const float4 v = gp[q * 16 + ec];
         r.x += v.x; r.y += v.y; r.z += v.z; r.w += v.w;
     }
-    red_out<ADAM>(a, rn, edge_to_flat(net, 4 * o) / 4, r);
+    red_out<ADAM, POP>(a, rn, edge_to_flat(net, 4 * o) / 4, r, st);
+}
+#ifndef NAV_LEARNER_POP
+template <bool ADAM>
+__global__ __launch_bounds__(kBlock) void k_grad_reduce(RedArgs a) {
+    grad_reduce_body<ADAM, false>(a, AdamStep{});
 }
 
 __global__ __launch_bounds__(kBlock) void k_adam(float4* __restrict__ p,
@@ -1436,6 +1406,7 @@ __global__ __launch_bounds__(kBlock) void k_strided_copy(const float* __restrict
     const int c = (int)(i % cols);
     dst[r * ldd + cd + c] = src[r * lds + cs + c];
 }
+#endif  // !NAV_LEARNER_POP
 
 inline int blocks_for(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
 inline int grid_stride_blocks(int64_t n) {
@@ -1467,8 +1438,8 @@ struct PackSet {
         ++a.n;
         return true;
     }
-    int launch(hipStream_t st) {
-        if (a.n == 0) return 0;
+    // the grid's shape from the jobs: 16-column groups and workgroups per network
+    void shape() {
         int hp = 0, nh = 0;
         for (int i = 0; i < a.n; ++i) {
             hp = a.j[i].pk.hp > hp ? a.j[i].pk.hp : hp;
@@ -1476,10 +1447,16 @@ struct PackSet {
         }
         a.cg = (hp + 15) / 16;
         a.per_net = (nh - 1) * 2 * a.cg;
+    }
+#ifndef NAV_LEARNER_POP
+    int launch(hipStream_t st) {
+        if (a.n == 0) return 0;
+        shape();
         hipLaunchKernelGGL(k_pack_img, dim3((unsigned)(a.n * a.per_net)), dim3(kBlock), 0, st, a);
         NAV_CHECK_LAUNCH();
         return 0;
     }
+#endif
 };
 
 bool red_net(const nav_mlp* net, const float* hs, int splits, const float* es, float* grad,
@@ -1499,6 +1476,7 @@ bool red_net(const nav_mlp* net, const float* hs, int splits, const float* es, f
 
 extern "C" {
 
+#ifndef NAV_LEARNER_POP
 int32_t nav_mlp_wgrad_splits(int32_t n_nets, int32_t d_out, int32_t hidden_pad, int32_t n_hidden,
                              int64_t M) {
     if (n_nets < 1 || n_nets > 2 || d_out < 1 || d_out > 2 || hidden_pad < 32 ||
@@ -1512,6 +1490,7 @@ int32_t nav_mlp_wgrad_splits(int32_t n_nets, int32_t d_out, int32_t hidden_pad, 
     if (s > by_rows) s = by_rows;
     return (int32_t)(s < 1 ? 1 : s);
 }
+#endif
 
 static int wgrad_args(const nav_mlp* nets, int32_t n_nets, int64_t M, const float* in,
                       int32_t ld_in, int32_t in_col, const float* const* acts,
@@ -1566,6 +1545,7 @@ static int wgrad_args(const nav_mlp* nets, int32_t n_nets, int64_t M, const floa
     return 0;
 }
 
+#ifndef NAV_LEARNER_POP
 int nav_mlp_wgrad(const nav_mlp* nets, int32_t n_nets, int64_t M, const float* in,
                   int32_t ld_in, int32_t in_col, const float* const* acts,
                   const float* const* dz, const float* const* dy, int32_t ld_dy,
@@ -1708,6 +1688,8 @@ int nav_adam_polyak_multi(const nav_mlp* nets, int32_t n_nets, const float* cons
                            grad_div, net_targets, targets, sources, n_pairs, tau, stream);
 }
 
+#endif  // !NAV_LEARNER_POP
+
 // RedArgs of the reduce (+ Adam when m is non-NULL, + the soft updates): *blocks = the reduce
 // blocks of k_grad_reduce (a.red_blocks) plus its soft-update blocks
 static int red_args(const nav_mlp* nets, int32_t n_nets, const float* const* hidden_slabs,
@@ -1775,6 +1757,7 @@ static int red_args(const nav_mlp* nets, int32_t n_nets, const float* const* hid
     return 0;
 }
 
+#ifndef NAV_LEARNER_POP
 static int grad_reduce_adam_impl(const nav_mlp* nets, int32_t n_nets, const float* const* hidden_slabs,
                           int32_t splits, const float* const* edge_slabs, int64_t edge_blocks,
                           float* const* grads, float* const* m, float* const* v, float beta1,
@@ -1917,9 +1900,11 @@ int nav_strided_copy(const float* src, int32_t ld_src, int32_t col_src, float* d
     return 0;
 }
 
+#endif  // !NAV_LEARNER_POP
+
 }  // extern "C"
 
-#ifdef NAV_WGRAD_TRACE
+#if defined(NAV_WGRAD_TRACE) && !defined(NAV_LEARNER_POP)
 extern "C" int nav_wgrad_trace_read(unsigned long long* host, int n) {
     const size_t bytes = sizeof(g_wgrad_trace);
     if (!host || (size_t)n * sizeof(unsigned long long) < bytes) return NAV_EINVAL;
@@ -1927,3 +1912,228 @@ extern "C" int nav_wgrad_trace_read(unsigned long long* host, int n) {
     return e == hipSuccess ? 0 : -(int)e;
 }
 #endif
+
+#ifdef NAV_LEARNER_POP
+// ---------------- the population learner's cross-row kernels ----------------
+// The kernels above with one more grid dimension, the member (blockIdx.y): a workgroup reads its
+// member's argument struct from the device table through a block-uniform pointer and runs the
+// same body on it. Built into an object of its own (learner_pop.o), so the plain kernels' object
+// holds what it held before.
+namespace {
+
+constexpr int kMaxMembers = 256;
+
+struct LearnMember {
+    WgradArgs wg[2];   // group 0: the twin critics, group 1: the actor
+    RedArgs red[3];    // the critics' step, the actor's, the actor's with the three soft updates
+    PackArgs pack[3];  // the images each of those rewrites (<= 4 networks)
+    double lr[2];      // critic_lr, actor_lr: step_size = (float)(lr / bc1) on the device
+};
+static_assert(sizeof(LearnMember) % 4 == 0, "copied as 32-bit words");
+
+template <bool GEN>
+__global__ __launch_bounds__(WG_THREADS) void k_wgrad_pop(const LearnMember* __restrict__ tab,
+                                                          int group) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const WgradArgs& a = tab[blockIdx.y].wg[group];
+    wgrad_tile<GEN>(a, wgrad_job(a, blockIdx.x, gridDim.x), smem);
+}
+template <int NI, int D, int KH>
+__global__ __launch_bounds__(WG_THREADS) void k_wgrad_fact_pop(const LearnMember* __restrict__ tab,
+                                                               int group) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ uint4 ftab[256];
+    const WgradArgs& a = tab[blockIdx.y].wg[group];
+    wgrad_tile_fact<NI, D, KH>(a, wgrad_job(a, blockIdx.x, gridDim.x), smem, ftab);
+}
+
+__global__ __launch_bounds__(kBlock) void k_grad_reduce_adam_pop(
+    const LearnMember* __restrict__ tab, int which, AdamStep st, double bc1) {
+    const LearnMember& m = tab[blockIdx.y];
+    // lr / (1 - b1^t) in f64, then to f32: the host's two roundings (_Adam.advance, c_float)
+    st.step_size = (float)(m.lr[which ? 1 : 0] / bc1);
+    grad_reduce_body<true, true>(m.red[which], st);
+}
+
+__global__ __launch_bounds__(kBlock) void k_pack_img_pop(const LearnMember* __restrict__ tab,
+                                                         int set) {
+    const PackArgs& a = tab[blockIdx.y].pack[set];
+#include "pack_img_body.inc"
+}
+
+// One member's entry (every check of the single-member entry points on the way); blocks[w]: grid.x
+// of reduce launch w
+int learn_member_fill(const nav_td3_member& t, int64_t B, int32_t sc, int32_t sa, LearnMember& e,
+                      int (&blocks)[3]) {
+    if (B < 1 || sc < 1 || sa < 1 || !t.batch || !t.batch_actor || !t.da) return NAV_EINVAL;
+    const int64_t nblk = nav_mlp_row_blocks(B);
+    const nav_mlp crit[2] = {t.critics[0], t.critics[1]};
+    const nav_mlp tcrit[2] = {t.target_critics[0], t.target_critics[1]};
+    if (t.actor.n_hidden != t.critics[0].n_hidden || t.actor.d_in != 2 || t.actor.d_out != 2 ||
+        crit[0].d_in != 4 || crit[0].d_out != 1 || crit[1].d_in != 4 || crit[1].d_out != 1)
+        return NAV_EINVAL;
+    if (t.actor.n_hidden > 1) {
+        int rc = wgrad_args(crit, 2, B, t.batch, 8, 0, t.acts, t.dz, t.dq, 1, t.masks,
+                            t.hidden_slabs, sc, e.wg[0]);
+        if (rc) return rc;
+        const float* acts_a[1] = {t.acts_actor};
+        const float* dz_a[1] = {t.dz_actor};
+        const float* dy_a[1] = {t.da};
+        const uint16_t* mk_a[1] = {t.masks_actor};
+        float* hs_a[1] = {t.hidden_slabs[0]};
+        rc = wgrad_args(&t.actor, 1, B, t.batch_actor, 8, 0, acts_a, dz_a, dy_a, 2, mk_a, hs_a,
+                        sa, e.wg[1]);
+        if (rc) return rc;
+    }
+    const float zero[2] = {0.f, 0.f};
+    PackSet ps[3];
+    int rc = red_args(crit, 2, t.hidden_slabs, sc, t.edge_slabs, nblk, t.grad_critic, t.m_critic,
+                      t.v_critic, 0.f, 0.f, 0.f, zero, zero, nullptr, nullptr, nullptr, 0, 0.f,
+                      e.red[0], &blocks[0], &ps[0]);
+    if (rc) return rc;
+    const float* hs_a[1] = {t.hidden_slabs[0]};
+    const float* es_a[1] = {t.edge_slabs_actor};
+    float* g_a[1] = {t.grad_actor};
+    float* m_a[1] = {t.m_actor};
+    float* v_a[1] = {t.v_actor};
+    rc = red_args(&t.actor, 1, hs_a, sa, es_a, nblk, g_a, m_a, v_a, 0.f, 0.f, 0.f, zero, zero,
+                  nullptr, nullptr, nullptr, 0, 0.f, e.red[1], &blocks[1], &ps[1]);
+    if (rc) return rc;
+    rc = red_args(&t.actor, 1, hs_a, sa, es_a, nblk, g_a, m_a, v_a, 0.f, 0.f, 0.f, zero, zero,
+                  &t.target_actor, tcrit, crit, 2, t.tau, e.red[2], &blocks[2], &ps[2]);
+    if (rc) return rc;
+    for (int w = 0; w < 3; ++w) {
+        ps[w].shape();
+        e.pack[w] = ps[w].a;
+    }
+    e.lr[0] = t.critic_lr;
+    e.lr[1] = t.actor_lr;
+    return 0;
+}
+
+bool same_shape(const nav_mlp& a, const nav_mlp& b) {
+    return a.d_in == b.d_in && a.d_out == b.d_out && a.hidden == b.hidden &&
+           a.hidden_pad == b.hidden_pad && a.n_hidden == b.n_hidden;
+}
+
+// the check every entry point shares; e0 / blocks: member 0's entry (the launch shape)
+int learn_pop_check(const nav_td3_member* members, int32_t n_members, int64_t B, int32_t sc,
+                    int32_t sa, LearnMember* dst, LearnMember& e0, int (&blocks)[3]) {
+    if (!members || n_members < 1 || n_members > kMaxMembers || B < 1) return NAV_EINVAL;
+    for (int m = 0; m < n_members; ++m) {
+        const nav_td3_member& t = members[m];
+        const nav_td3_member& t0 = members[0];
+        if (!same_shape(t.actor, t0.actor) || !same_shape(t.target_actor, t0.target_actor))
+            return NAV_EINVAL;
+        for (int i = 0; i < 2; ++i)
+            if (!same_shape(t.critics[i], t0.critics[i]) ||
+                !same_shape(t.target_critics[i], t0.target_critics[i]))
+                return NAV_EINVAL;
+        LearnMember e{};
+        int bl[3] = {0, 0, 0};
+        const int rc = learn_member_fill(t, B, sc, sa, e, bl);
+        if (rc) return rc;
+        if (m == 0) {
+            e0 = e;
+            for (int w = 0; w < 3; ++w) blocks[w] = bl[w];
+        }
+        if (dst) dst[m] = e;
+    }
+    return 0;
+}
+
+// the table's second section: past the members' row-kernel arguments
+const LearnMember* learn_section(const void* table, int32_t n_members) {
+    return reinterpret_cast<const LearnMember*>(static_cast<const char*>(table) +
+                                                (int64_t)n_members * navi_rows_pop_entry_bytes());
+}
+
+}  // namespace
+
+int64_t navi_learner_pop_entry_bytes() { return (int64_t)sizeof(LearnMember); }
+
+int navi_learner_pop_fill(const nav_td3_member* members, int32_t n_members, int64_t B,
+                          int32_t splits_critic, int32_t splits_actor, void* dst) {
+    LearnMember e0;
+    int blocks[3];
+    return learn_pop_check(members, n_members, B, splits_critic, splits_actor,
+                           static_cast<LearnMember*>(dst), e0, blocks);
+}
+
+extern "C" {
+
+int32_t nav_mlp_wgrad_splits_pop(int32_t n_members, int32_t n_nets, int32_t d_out,
+                                 int32_t hidden_pad, int32_t n_hidden, int64_t M) {
+    if (n_members < 1 || n_members > kMaxMembers || n_nets < 1 || n_nets > 2 || d_out < 1 ||
+        d_out > 2 || hidden_pad < 32 || hidden_pad > 256 || (hidden_pad & 31) || n_hidden < 1 ||
+        M < 0)
+        return NAV_EINVAL;
+    if (n_hidden < 2) return 1;
+    const int64_t jobs = (int64_t)n_members * n_nets * wgrad_tiling(d_out, hidden_pad, n_hidden).jobs;
+    // WG_TOTAL workgroups over all members' tile jobs, at least 512 rows per split
+    int64_t s = WG_TOTAL / jobs;
+    const int64_t by_rows = (M + 511) / 512;
+    if (s > by_rows) s = by_rows;
+    return (int32_t)(s < 1 ? 1 : s);
+}
+
+int nav_mlp_wgrad_pop(const nav_td3_member* members, int32_t n_members, int64_t B,
+                      const void* table, int32_t group, int32_t splits, void* stream) {
+    LearnMember e0;
+    int blocks[3];
+    if (!table || group < 0 || group > 1 || splits < 1) return NAV_EINVAL;
+    const int rc = learn_pop_check(members, n_members, B, group == 0 ? splits : 1,
+                                   group == 1 ? splits : 1, nullptr, e0, blocks);
+    if (rc) return rc;
+    if (members[0].actor.n_hidden < 2) return 0;
+    const WgradArgs& a = e0.wg[group];
+    const int n_nets = group == 0 ? 2 : 1;
+    const int64_t per_member = (int64_t)n_nets * a.n_hid * splits;
+    const size_t lds = a.fact ? (size_t)WG_WAVES * WG_TILE * WG_TILE * 4 : wgrad_lds_bytes();
+    void (*k)(const LearnMember*, int) =
+        a.fact                   ? (a.tn == 256   ? k_wgrad_fact_pop<8, 1, 1>
+                                    : a.tn == 128 ? k_wgrad_fact_pop<4, 1, 2>
+                                                  : k_wgrad_fact_pop<2, 1, 2>)
+        : a.net[0].n_hidden >= 3 ? k_wgrad_pop<true>
+                                 : k_wgrad_pop<false>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const LearnMember* tab = learn_section(table, n_members);
+    hipLaunchKernelGGL(k, dim3((unsigned)per_member, (unsigned)n_members), dim3(WG_THREADS), lds,
+                       S(stream), tab, (int)group);
+    NAV_CHECK_LAUNCH();
+    return 0;
+}
+
+int nav_grad_reduce_adam_pop(const nav_td3_member* members, int32_t n_members, int64_t B,
+                             const void* table, int32_t group, float beta1, float beta2,
+                             float eps, double bc1, float bc2_sqrt, int32_t soft_update,
+                             void* stream) {
+    LearnMember e0;
+    int blocks[3];
+    if (!table || group < 0 || group > 1 || (soft_update && group != 1) || !(bc1 > 0.0) ||
+        !(bc2_sqrt > 0.f))
+        return NAV_EINVAL;
+    const int rc = learn_pop_check(members, n_members, B, 1, 1, nullptr, e0, blocks);
+    if (rc) return rc;
+    const int which = group == 0 ? 0 : soft_update ? 2 : 1;
+    AdamStep st{};
+    st.bc2s = bc2_sqrt;
+    st.b1w = 1.0f - beta1;
+    st.b2 = beta2;
+    st.omb2 = 1.0f - beta2;
+    st.eps = eps;
+    const LearnMember* tab = learn_section(table, n_members);
+    hipLaunchKernelGGL(k_grad_reduce_adam_pop, dim3((unsigned)blocks[which], (unsigned)n_members),
+                       dim3(kBlock), 0, S(stream), tab, which, st, bc1);
+    NAV_CHECK_LAUNCH();
+    const PackArgs& pk = e0.pack[which];
+    if (pk.n == 0) return 0;  // n_hidden == 1: no packed image
+    hipLaunchKernelGGL(k_pack_img_pop, dim3((unsigned)(pk.n * pk.per_net), (unsigned)n_members),
+                       dim3(kBlock), 0, S(stream), tab, which);
+    NAV_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // extern "C"
+#endif  // NAV_LEARNER_POP

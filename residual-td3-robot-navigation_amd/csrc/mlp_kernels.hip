@@ -1864,6 +1864,18 @@ struct CriticRowsArgs {
 };
 static_assert(sizeof(CriticRowsArgs) <= 4096, "kernel argument size");
 
+// The population forms of critic_rows / actor_rows (nav_td3_critic_rows_pop / _actor_rows_pop):
+// grid.z is the member, whose CriticRowsArgs / ActorRowsArgs the workgroup reads from the device
+// table (nav_td3_pop_table_build) through a block-uniform pointer. What changes per launch and is
+// common to all members travels by value, so the table is not rewritten while training: the
+// replay fill, the Philox counter, and the twins' form (chosen from all members' workgroups).
+struct RowsPop {
+    const void* table;  // [n_members] CriticRowsArgs or ActorRowsArgs
+    int64_t size;
+    uint32_t counter;
+    int32_t split_twins;
+};
+
 // train_critic (robot.py:329-361) for one block of TM batch rows: sample, target policy
 // smoothing through the target actor, twin target critics, TD target, then the twin online
 // critics with mse_loss's gradient, the loss and the output layers' gradient partials, and
@@ -1871,128 +1883,21 @@ static_assert(sizeof(CriticRowsArgs) <= 4096, "kernel argument size");
 // forward, while its rows and ReLU bits are fresh.
 // CBM: the critics' row-backward form (bwd_net's BM: 0 for one hidden layer, else 1), chosen by
 // the launcher from n_hidden
+// The kernel's statements are td3_critic_rows_body.inc, once per form: the plain kernel's stay
+// token for token what they were (its machine code is pinned, tools/isa_diff.py), the population
+// form (POP) reads `a` from the member's table entry and the launch's values from `pv` (the
+// entry's rsize, counters, split_twins and warm list are then unused).
 template <int NT, int RT, int CBM>
 __global__ __launch_bounds__(kBlock, 1) void k_td3_critic_rows(CriticRowsArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    if (a.warm.n && (int)blockIdx.y >= a.warm.y0) {  // an L2 warmer row (small grids)
-        warm_l2(a.warm);
-        return;
-    }
-    constexpr int hp = NT * 32, SS = hp + 4, TM = RT * 32;
-    const int tid = threadIdx.x;
-    const int64_t B = a.B, row0 = (int64_t)blockIdx.x * TM, rt0 = (int64_t)blockIdx.x * RT;
-    const int64_t n_rt = mask_rowtiles(B);
-    float* act = smem;
-    float* xin = act + TM * SS;    // [TM][4] network input rows
-    float* red = xin + TM * 4;     // [2][PARTS][TM] output partial sums
-    float* brow = red + red_floats(TM);  // [TM][8] the sampled replay rows
-    float* qv = brow + TM * 8;     // [TM] q1'
-    float* dys = qv + TM;          // [TM][4] dL/dq rows of the row backward
-    _Float16* stage = reinterpret_cast<_Float16*>(dys + TM * 4);  // gemm_cols' split stage
-    NAV_MARK(0);
-    NAV_CLOCK(0, 0);
-    const L0Pre l0_at = load_l0<NT>(a.actor_t);  // in flight under the sampling
-    // the sampled replay row of thread tid < TM: its gather is issued first, so it is in flight
-    // while the smoothing noise below is formed
-    float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
-    if (tid < TM && row0 + tid < B)
-        sample_row(a.rows, a.rsize, a.idx, a.seed_lo, a.seed_hi, a.sample_ctr, row0 + tid, lo, hi);
-    // target policy smoothing noise of (row, output) (tid - TM) % TM, (tid - TM) / TM: clamp(
-    // policy_noise * eps, +-noise_clip) — threads past the sampling ones, so its f64 Box-Muller
-    // runs on other waves (other SIMDs) than the sampling's Philox draw and gather
-    static_assert(3 * TM <= kBlock, "sampling threads, then the noise's");
-    float tnz = 0.f;
-    const int tn = tid - TM;
-    if (tn >= 0 && tn < 2 * TM && row0 + tn % TM < B) {
-        const int64_t r = row0 + tn % TM;
-        const int j = tn / TM;
-        float e;
-        if (a.eps) {
-            e = a.eps[r * 2 + j];
-        } else {
-            const double2 z = gauss_pair(philox((uint32_t)r, 0u, NAV_TAG_TNOISE, a.noise_ctr,
-                                                a.seed_lo, a.seed_hi));
-            e = (float)(j == 0 ? z.x : z.y);
-        }
-        tnz = fminf(fmaxf(e * a.policy_noise, -a.noise_clip), a.noise_clip);
-    }
-    if (tid < TM) {
-        const int64_t b = row0 + tid;
-        if (b < B && blockIdx.y == 0) {  // split twins: one writer per batch row
-            float4* dst = reinterpret_cast<float4*>(a.batch) + 2 * b;
-            dst[0] = lo;
-            dst[1] = hi;
-        }
-        *reinterpret_cast<float4*>(brow + tid * 8) = lo;
-        *reinterpret_cast<float4*>(brow + tid * 8 + 4) = hi;
-        *reinterpret_cast<float4*>(xin + tid * 4) = make_float4(hi.y, hi.z, 0.f, 0.f);  // s'
-    }
-    __syncthreads();
-    NAV_MARK(1);
-    // target actor; a' = clamp(pi'(s') + clamp(policy_noise * eps, +-noise_clip), +-max_action).
-    // Each pass's layer-0 constants are loaded one pass ahead (L0Pre).
-    f32x16 top[RT][2];
-    const L0Pre l0_ct1 = load_l0<NT>(a.critic_t[0]);
-    fwd_net<NT, RT, kPfWide, 2>(a.actor_t, act, stage, xin, red, nullptr, n_rt, nullptr, 0u, row0, B, rt0, top, 2,
-                    &l0_at);
-    if (tn >= 0 && tn < 2 * TM) {  // the noise's threads
-        const int rloc = tn % TM, j = tn / TM;
-        const int64_t r = row0 + rloc;
-        float v = 0.f;
-        if (r < B) {
-            const float y = out_y<RT>(a.actor_t, red, rloc, j);
-            v = y + tnz;
-            v = fminf(fmaxf(v, -a.max_action), a.max_action);
-        }
-        xin[rloc * 4 + 2 + j] = v;
-    }
-    __syncthreads();
-    NAV_MARK(8);
-    // twin target critics on (s', a'), then y = r + gamma * min(q1', q2') * (1 - done), kept in
-    // the row's thread
-    const L0Pre l0_ct2 = load_l0<NT>(a.critic_t[1]);
-    fwd_net<NT, RT, kPfWide, 4>(a.critic_t[0], act, stage, xin, red, nullptr, n_rt, nullptr, 0u, row0, B, rt0, top,
-                    9, &l0_ct1);
-    if (tid < TM) qv[tid] = out_y<RT>(a.critic_t[0], red, tid, 0);
-    const int q0 = a.split_twins ? (int)blockIdx.y : 0;  // the first online critic of the block
-    L0Pre l0_on = load_l0<NT>(a.critic[q0]);
-    fwd_net<NT, RT, kPfWide, 4>(a.critic_t[1], act, stage, xin, red, nullptr, n_rt, nullptr, 0u, row0, B, rt0, top,
-                    15, &l0_ct2);
-    float yt = 0.f;
-    if (tid < TM) {
-        const float q2 = out_y<RT>(a.critic_t[1], red, tid, 0);
-        const float rw = brow[tid * 8 + 4], dn = brow[tid * 8 + 7];
-        yt = rw + (a.gamma * fminf(qv[tid], q2)) * (1.0f - dn);
-        *reinterpret_cast<float4*>(xin + tid * 4) = *reinterpret_cast<const float4*>(brow + tid * 8);
-    }
-    __syncthreads();
-    NAV_MARK(21);
-    // online critics on (s, a): both, or (split_twins) the one of this workgroup's grid row
-#pragma unroll 1
-    for (int q = 0; q < 2; ++q) {
-        if (a.split_twins && q != (int)blockIdx.y) continue;  // workgroup-uniform
-        uint32_t top_bits[RT * 2];
-        WoCols wo;
-        fwd_net<NT, RT, kPfWide, 4>(a.critic[q], act, stage, xin, red, a.masks[q], n_rt, a.acts[q], a.save_mask, row0,
-                        B, rt0, top, 22 + 14 * q, &l0_on, top_bits, &wo);
-        if (q == 0 && !a.split_twins) l0_on = load_l0<NT>(a.critic[1]);
-        float* es = a.eslab[q] ? a.eslab[q] + (int64_t)blockIdx.x * a.ecount : nullptr;
-        loss_epilogue<NT, RT>(a.critic[q], top, red, row0, B, yt, a.norm, a.dq[q],
-                              a.loss_part[q] + blockIdx.x, es);
-        __syncthreads();
-        NAV_MARK(28 + 14 * q);
-        if (a.row_backward) {
-            if (tid < TM)
-                *reinterpret_cast<float4*>(dys + tid * 4) =
-                    make_float4(red[kWaves * TM + tid], 0.f, 0.f, 0.f);  // loss_epilogue's dq
-            __syncthreads();
-            bwd_net<NT, RT, kPfWide, CBM>(a.critic[q], act, stage, dys, xin, a.masks[q], n_rt, es, nullptr, a.dz[q],
-                            a.dz_save_mask, row0, B, rt0, 29 + 14 * q, top_bits, &wo, false);
-            __syncthreads();  // the next forward's layer 0 overwrites the rows
-        }
-        NAV_MARK(35 + 14 * q);
-    }
-    NAV_CLOCK(0, 1);
+    constexpr bool POP = false;
+    constexpr RowsPop pv{};
+#include "td3_critic_rows_body.inc"
+}
+template <int NT, int RT, int CBM>
+__global__ __launch_bounds__(kBlock, 1) void k_td3_critic_rows_pop(RowsPop pv) {
+    constexpr bool POP = true;
+    const CriticRowsArgs& a = static_cast<const CriticRowsArgs*>(pv.table)[blockIdx.z];
+#include "td3_critic_rows_body.inc"
 }
 
 struct ActorRowsArgs {
@@ -2021,85 +1926,27 @@ struct ActorRowsArgs {
 // critic-1 forward on (s, pi(s)), backward of -mean(Q) through critic 1 to its action input
 // (critic grads discarded, as zero_grad does), and the actor's row backward with its edge
 // partials.
+// (td3_actor_rows_body.inc once per form, as k_td3_critic_rows)
 template <int NT, int RT, int CBM>
 __global__ __launch_bounds__(kBlock, 1) void k_td3_actor_rows(ActorRowsArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    if (a.warm.n && (int)blockIdx.y >= a.warm.y0) {  // an L2 warmer row (small grids)
-        warm_l2(a.warm);
-        return;
-    }
-    constexpr int hp = NT * 32, SS = hp + 4, TM = RT * 32;
-    const int tid = threadIdx.x;
-    const int64_t B = a.B, row0 = (int64_t)blockIdx.x * TM, rt0 = (int64_t)blockIdx.x * RT;
-    const int64_t n_rt = mask_rowtiles(B);
-    float* act = smem;
-    float* xin = act + TM * SS;      // [TM][4] (s, pi(s))
-    float* red = xin + TM * 4;       // [2][PARTS][TM]
-    float* dys = red + red_floats(TM);  // [TM][4] critic dy
-    float* dys2 = dys + TM * 4;      // [TM][4] actor dy = dL/da
-    _Float16* stage = reinterpret_cast<_Float16*>(dys2 + TM * 4);  // gemm_cols' split stage
-    const L0Pre l0_a = load_l0<NT>(a.actor);  // in flight under the sampling
-    NAV_CLOCK(1, 0);
-    if (tid < TM) {
-        const int64_t b = row0 + tid;
-        float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
-        if (b < B) {
-            sample_row(a.rows, a.rsize, a.idx, a.seed_lo, a.seed_hi, a.sample_ctr, b, lo, hi);
-            float4* dst = reinterpret_cast<float4*>(a.batch) + 2 * b;
-            dst[0] = lo;
-            dst[1] = hi;
-        }
-        *reinterpret_cast<float4*>(xin + tid * 4) = make_float4(lo.x, lo.y, 0.f, 0.f);  // s
-        *reinterpret_cast<float4*>(dys + tid * 4) =
-            make_float4(b < B ? a.dq : 0.f, 0.f, 0.f, 0.f);
-    }
-    __syncthreads();
-    // the actor's top hidden layer stays in registers until dL/da is known (its dWo partials)
-    f32x16 topa[RT][2];
-    fwd_net<NT, RT, 1, 2>(a.actor, act, stage, xin, red, a.masks_a, n_rt, a.acts, a.save_mask, row0, B, rt0,
-                    topa, -64, &l0_a);
-    const L0Pre l0_c = load_l0<NT>(a.critic);  // in flight under the action epilogue
-    if (tid < 2 * TM) {
-        const int rloc = tid % TM, j = tid / TM;
-        xin[rloc * 4 + 2 + j] = row0 + rloc < B ? out_y<RT>(a.actor, red, rloc, j) : 0.f;
-    }
-    __syncthreads();
-    // the critic's top-layer ReLU bits and Wo columns go from its forward to its row backward in
-    // registers (as in critic_rows)
-    f32x16 top[RT][2];
-    uint32_t top_bits[RT * 2];
-    WoCols wo;
-    fwd_net<NT, RT, 1, 4>(a.critic, act, stage, xin, red, a.masks_c, n_rt, nullptr, 0u, row0, B, rt0, top,
-                    -64, &l0_c, top_bits, &wo);
-    if (tid < TM && a.q && row0 + tid < B) a.q[row0 + tid] = out_y<RT>(a.critic, red, tid, 0);
-    bwd_net<NT, RT, 1, CBM>(a.critic, act, stage, dys, xin, a.masks_c, n_rt, nullptr, nullptr,
-                                    nullptr, 0u, row0, B, rt0, -64, top_bits, &wo);
-    if (tid < 2 * TM) {
-        const int rloc = tid % TM, j = tid / TM;
-        const int64_t r = row0 + rloc;
-        const float v = r < B ? dx_unit<NT>(a.critic, act, rloc, 2 + j) : 0.f;
-        dys2[rloc * 4 + j] = v;
-        if (r < B) a.da[r * 2 + j] = v;
-    }
-    if (tid < TM) {
-        dys2[tid * 4 + 2] = 0.f;
-        dys2[tid * 4 + 3] = 0.f;
-    }
-    __syncthreads();
-    // the actor's output layer gradient partials: dWo from its top-layer registers, dbo = column
-    // sums of dL/da (bwd_net's order)
-    float* es = a.eslab + (int64_t)blockIdx.x * a.ecount;
-    wo_grad_regs<NT, RT>(a.actor, topa, dys2, 4, es);
-    if (tid < 4) {
-        float sb = 0.f;
-        if (tid < a.actor.d_out)
-            for (int rr = 0; rr < TM; ++rr) sb += dys2[rr * 4 + tid];
-        es[e_bo(a.actor) + tid] = sb;
-    }
-    bwd_net<NT, RT>(a.actor, act, stage, dys2, xin, a.masks_a, n_rt, es, nullptr, a.dz, a.dz_save_mask,
-                    row0, B, rt0, -64, nullptr, nullptr, false);
-    NAV_CLOCK(1, 1);
+    constexpr bool POP = false;
+    constexpr RowsPop pv{};
+#include "td3_actor_rows_body.inc"
 }
+template <int NT, int RT, int CBM>
+__global__ __launch_bounds__(kBlock, 1) void k_td3_actor_rows_pop(RowsPop pv) {
+    constexpr bool POP = true;
+    const ActorRowsArgs& a = static_cast<const ActorRowsArgs*>(pv.table)[blockIdx.z];
+#include "td3_actor_rows_body.inc"
+}
+
+// what a population launch passes to the per-NT objects (the table's row sections are
+// [n_members] CriticRowsArgs, then [n_members] ActorRowsArgs)
+struct RowsPopLaunch {
+    RowsPop k;
+    int64_t B;
+    int n_hidden, n_members;
+};
 
 
 // ---- launch helpers (template dispatch on NT = hp / 32 and RT = rows / 32) ----
@@ -2117,7 +1964,10 @@ int row_tiles_for(int64_t M, bool tick) { return (!tick && M <= kSmallRows) ? 1 
 // their own objects (this file built with NAV_MLP_PART = NT, see the Makefile) so the heavy
 // template instantiations compile in parallel; the main object (NAV_MLP_PART = 0) dispatches to
 // them through nav_mlp_rows_<NT>(). Argument structs travel as const void* (same definitions).
-enum { FAM_FWD = 0, FAM_BWD = 1, FAM_CRITIC = 2, FAM_ACTOR = 3, FAM_TEST = 4, FAM_TEST_POP = 5 };
+enum {
+    FAM_FWD = 0, FAM_BWD = 1, FAM_CRITIC = 2, FAM_ACTOR = 3, FAM_TEST = 4, FAM_TEST_POP = 5,
+    FAM_CRITIC_POP = 6, FAM_ACTOR_POP = 7
+};
 
 }  // namespace
 
@@ -2125,7 +1975,9 @@ enum { FAM_FWD = 0, FAM_BWD = 1, FAM_CRITIC = 2, FAM_ACTOR = 3, FAM_TEST = 4, FA
     int nav_mlp_rows_##NT_(int fam, int rt, int in_mode, int out_mode, const void* args,      \
                            int n_nets, hipStream_t st);                                       \
     int nav_mlp_rows_pop_##NT_(int fam, int rt, int in_mode, int out_mode, const void* args,  \
-                               int n_nets, hipStream_t st);
+                               int n_nets, hipStream_t st);                                   \
+    int nav_mlp_rows_lpop_##NT_(int fam, int rt, int in_mode, int out_mode, const void* args, \
+                                int n_nets, hipStream_t st);
 NAV_ROWS_DECL(1) NAV_ROWS_DECL(2) NAV_ROWS_DECL(3) NAV_ROWS_DECL(4)
 NAV_ROWS_DECL(5) NAV_ROWS_DECL(6) NAV_ROWS_DECL(7) NAV_ROWS_DECL(8)
 #undef NAV_ROWS_DECL
@@ -2200,6 +2052,32 @@ void launch_actor_rows_k(const ActorRowsArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k, dim3(gx, 1u + wy), dim3(kBlock), lds, st, w);
 }
 
+// the population forms: grid.z = the member, no L2 warmer rows
+template <int NT, int RT>
+void launch_critic_rows_pop_k(const RowsPopLaunch& a, hipStream_t st) {
+    constexpr int TM = RT * 32;
+    const size_t lds =
+        ((size_t)TM * (NT * 32 + 4) + TM * 4 + red_floats(TM) + TM * 8 + TM + TM * 4) * 4 +
+        stage_bytes(TM, NT * 32);
+    auto k = a.n_hidden == 1 ? k_td3_critic_rows_pop<NT, RT, 0> : k_td3_critic_rows_pop<NT, RT, 1>;
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+    const unsigned gx = (unsigned)((a.B + TM - 1) / TM), gy = a.k.split_twins ? 2u : 1u;
+    hipLaunchKernelGGL(k, dim3(gx, gy, (unsigned)a.n_members), dim3(kBlock), lds, st, a.k);
+}
+
+template <int NT, int RT>
+void launch_actor_rows_pop_k(const RowsPopLaunch& a, hipStream_t st) {
+    constexpr int TM = RT * 32;
+    const size_t lds = ((size_t)TM * (NT * 32 + 4) + TM * 4 + red_floats(TM) + TM * 8) * 4 +
+                       stage_bytes(TM, NT * 32);
+    auto k = a.n_hidden == 1 ? k_td3_actor_rows_pop<NT, RT, 0> : k_td3_actor_rows_pop<NT, RT, 1>;
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+    const unsigned gx = (unsigned)((a.B + TM - 1) / TM);
+    hipLaunchKernelGGL(k, dim3(gx, 1u, (unsigned)a.n_members), dim3(kBlock), lds, st, a.k);
+}
+
 template <int NT, int RT, bool POP>
 void launch_test_k(const TestArgs& a, hipStream_t st) {
     constexpr int TM = RT * 32;
@@ -2213,7 +2091,18 @@ void launch_test_k(const TestArgs& a, hipStream_t st) {
 template <int RT>
 int rows_rt(int fam, int in_mode, int out_mode, const void* args, int n_nets, hipStream_t st) {
     constexpr int NT = NAV_MLP_PART;
-#ifdef NAV_MLP_POP
+#if defined(NAV_MLP_LPOP)
+    // the population learner's row kernels, in objects of their own too (mlp_lpop<NT>.o)
+    if (fam == FAM_CRITIC_POP) {
+        launch_critic_rows_pop_k<NT, RT>(*static_cast<const RowsPopLaunch*>(args), st);
+        return 0;
+    }
+    if (fam == FAM_ACTOR_POP) {
+        launch_actor_rows_pop_k<NT, RT>(*static_cast<const RowsPopLaunch*>(args), st);
+        return 0;
+    }
+    return NAV_EINVAL;
+#elif defined(NAV_MLP_POP)
     // The population instantiations live in objects of their own (mlp_pop<NT>.o): compiled beside
     // them, the plain tick kernel came out with a few scalar loads scheduled elsewhere, and the
     // bench's kernels are to stay exactly as the compiler made them (tools/isa_diff.py).
@@ -2270,7 +2159,9 @@ int rows_rt(int fam, int in_mode, int out_mode, const void* args, int n_nets, hi
 
 #define NAV_CAT2(a, b) a##b
 #define NAV_CAT(a, b) NAV_CAT2(a, b)
-#ifdef NAV_MLP_POP
+#if defined(NAV_MLP_LPOP)
+#define NAV_ROWS_NAME NAV_CAT(nav_mlp_rows_lpop_, NAV_MLP_PART)
+#elif defined(NAV_MLP_POP)
 #define NAV_ROWS_NAME NAV_CAT(nav_mlp_rows_pop_, NAV_MLP_PART)
 #else
 #define NAV_ROWS_NAME NAV_CAT(nav_mlp_rows_, NAV_MLP_PART)
@@ -2282,7 +2173,7 @@ int NAV_ROWS_NAME(int fam, int rt, int in_mode, int out_mode, const void* args, 
 }
 
 // (a trace variant builds one part with NAV_PHASE_TRACE: tools/build_variant.sh)
-#if defined(NAV_PHASE_TRACE) && !defined(NAV_MLP_POP)
+#if defined(NAV_PHASE_TRACE) && !defined(NAV_MLP_POP) && !defined(NAV_MLP_LPOP)
 extern "C" int nav_phase_trace_read(unsigned long long* host, int n) {
     const size_t bytes = sizeof(g_phase_trace);
     if (!host || (size_t)n * sizeof(unsigned long long) < bytes) return NAV_EINVAL;
@@ -2291,7 +2182,8 @@ extern "C" int nav_phase_trace_read(unsigned long long* host, int n) {
 }
 #endif
 
-#if defined(NAV_CLOCK_STAMP) && NAV_MLP_PART == 8 && !defined(NAV_MLP_POP)
+#if defined(NAV_CLOCK_STAMP) && NAV_MLP_PART == 8 && !defined(NAV_MLP_POP) && \
+    !defined(NAV_MLP_LPOP)
 extern "C" int nav_clock_stamp_read(unsigned long long* host, int n) {
     const size_t bytes = sizeof(g_clock_stamp);
     if (!host || (size_t)n * sizeof(unsigned long long) < bytes) return NAV_EINVAL;
@@ -2305,17 +2197,20 @@ extern "C" int nav_clock_stamp_read(unsigned long long* host, int n) {
 namespace {
 
 // hp / 32 -> the per-NT object; the population forms of the tick and the test rollout live in
-// objects of their own (row 1)
+// objects of their own (row 1), and so do the population learner's row kernels (row 2)
 int rows_dispatch(int hp, int fam, int in_mode, int out_mode, const void* args, int n_nets,
                   int64_t M, hipStream_t st) {
-    static decltype(&nav_mlp_rows_1) const rows[2][8] = {
+    static decltype(&nav_mlp_rows_1) const rows[3][8] = {
         {nav_mlp_rows_1, nav_mlp_rows_2, nav_mlp_rows_3, nav_mlp_rows_4, nav_mlp_rows_5,
          nav_mlp_rows_6, nav_mlp_rows_7, nav_mlp_rows_8},
         {nav_mlp_rows_pop_1, nav_mlp_rows_pop_2, nav_mlp_rows_pop_3, nav_mlp_rows_pop_4,
-         nav_mlp_rows_pop_5, nav_mlp_rows_pop_6, nav_mlp_rows_pop_7, nav_mlp_rows_pop_8}};
+         nav_mlp_rows_pop_5, nav_mlp_rows_pop_6, nav_mlp_rows_pop_7, nav_mlp_rows_pop_8},
+        {nav_mlp_rows_lpop_1, nav_mlp_rows_lpop_2, nav_mlp_rows_lpop_3, nav_mlp_rows_lpop_4,
+         nav_mlp_rows_lpop_5, nav_mlp_rows_lpop_6, nav_mlp_rows_lpop_7, nav_mlp_rows_lpop_8}};
     const int rt = row_tiles_for(
         M, fam == FAM_FWD && (out_mode == OUT_TICK || out_mode == OUT_TICK_POP));
-    const bool pop = fam == FAM_TEST_POP || (fam == FAM_FWD && out_mode == OUT_TICK_POP);
+    const int pop = fam == FAM_CRITIC_POP || fam == FAM_ACTOR_POP ? 2
+                    : fam == FAM_TEST_POP || (fam == FAM_FWD && out_mode == OUT_TICK_POP) ? 1 : 0;
     if (hp < 32 || hp > 256 || (hp & 31)) return NAV_EINVAL;
     const int r = rows[pop][hp / 32 - 1](fam, rt, in_mode, out_mode, args, n_nets, st);
     if (r) return r;
@@ -2427,7 +2322,29 @@ int pop_check(const nav_params* params, const nav_mlp* actors, const nav_replay*
 
 }  // namespace
 
+int64_t navi_rows_pop_entry_bytes() {
+    static_assert(sizeof(CriticRowsArgs) % 8 == 0 && sizeof(ActorRowsArgs) % 8 == 0,
+                  "the table's sections stay 8-byte aligned");
+    return (int64_t)(sizeof(CriticRowsArgs) + sizeof(ActorRowsArgs));
+}
+
 extern "C" {
+
+static int critic_rows_args(const nav_mlp* target_actor, const nav_mlp* target_critics,
+                            const nav_mlp* critics, const nav_replay* replay, int64_t size,
+                            int64_t B, const int64_t* idx, uint32_t seed_lo, uint32_t seed_hi,
+                            uint32_t counter, const float* eps, float policy_noise,
+                            float noise_clip, float max_action, float gamma, float* batch,
+                            float* const* dq, float* const* loss_part, float* const* edge_slabs,
+                            float* const* acts, uint32_t save_mask, uint16_t* const* masks,
+                            int32_t row_backward, float* const* dz, uint32_t dz_save_mask,
+                            int32_t split_twins, CriticRowsArgs& a);
+static int actor_rows_args(const nav_mlp* actor, const nav_mlp* critic, const nav_replay* replay,
+                           int64_t size, int64_t B, const int64_t* idx, uint32_t seed_lo,
+                           uint32_t seed_hi, uint32_t counter, float* batch, float* q, float* da,
+                           float* acts, uint32_t save_mask, float* dz, uint32_t dz_save_mask,
+                           uint16_t* masks_actor, uint16_t* masks_critic, float* edge_slabs,
+                           ActorRowsArgs& a);
 
 int64_t nav_mlp_param_count(int32_t d_in, int32_t d_out, int32_t hp, int32_t n_hidden) {
     nav_mlp n{d_in, d_out, hp, hp, n_hidden, reinterpret_cast<float*>(16),
@@ -2699,6 +2616,25 @@ int nav_td3_critic_rows(const nav_mlp* target_actor, const nav_mlp* target_criti
                         int32_t row_backward, float* const* dz, uint32_t dz_save_mask,
                         int32_t split_twins, void* stream) {
     CriticRowsArgs a{};
+    const int rc = critic_rows_args(target_actor, target_critics, critics, replay, size, B, idx,
+                                    seed_lo, seed_hi, counter, eps, policy_noise, noise_clip,
+                                    max_action, gamma, batch, dq, loss_part, edge_slabs, acts,
+                                    save_mask, masks, row_backward, dz, dz_save_mask, split_twins,
+                                    a);
+    if (rc) return rc;
+    return rows_dispatch(a.actor_t.hp, FAM_CRITIC, 0, 0, &a, 1, a.B, S(stream));
+}
+
+// nav_td3_critic_rows' argument check and kernel arguments (the population table's too)
+static int critic_rows_args(const nav_mlp* target_actor, const nav_mlp* target_critics,
+                            const nav_mlp* critics, const nav_replay* replay, int64_t size,
+                            int64_t B, const int64_t* idx, uint32_t seed_lo, uint32_t seed_hi,
+                            uint32_t counter, const float* eps, float policy_noise,
+                            float noise_clip, float max_action, float gamma, float* batch,
+                            float* const* dq, float* const* loss_part, float* const* edge_slabs,
+                            float* const* acts, uint32_t save_mask, uint16_t* const* masks,
+                            int32_t row_backward, float* const* dz, uint32_t dz_save_mask,
+                            int32_t split_twins, CriticRowsArgs& a) {
     if (row_backward && dz_save_mask && !dz) return NAV_EINVAL;
     if (!target_actor || !target_critics || !critics || !replay || !replay->rows || B < 1 ||
         size < 1 || size > replay->capacity || size > ((int64_t)1 << 32) || !batch || !dq ||
@@ -2748,7 +2684,7 @@ int nav_td3_critic_rows(const nav_mlp* target_actor, const nav_mlp* target_criti
     a.batch = batch;
     a.ecount = edge_count(a.critic[0]);
     a.save_mask = save_mask;
-    return rows_dispatch(a.actor_t.hp, FAM_CRITIC, 0, 0, &a, 1, a.B, S(stream));
+    return 0;
 }
 
 int nav_td3_actor_rows(const nav_mlp* actor, const nav_mlp* critic, const nav_replay* replay,
@@ -2758,6 +2694,19 @@ int nav_td3_actor_rows(const nav_mlp* actor, const nav_mlp* critic, const nav_re
                        uint16_t* masks_actor, uint16_t* masks_critic, float* edge_slabs,
                        void* stream) {
     ActorRowsArgs a{};
+    const int rc = actor_rows_args(actor, critic, replay, size, B, idx, seed_lo, seed_hi, counter,
+                                   batch, q, da, acts, save_mask, dz, dz_save_mask, masks_actor,
+                                   masks_critic, edge_slabs, a);
+    if (rc) return rc;
+    return rows_dispatch(a.actor.hp, FAM_ACTOR, 0, 0, &a, 1, a.B, S(stream));
+}
+
+static int actor_rows_args(const nav_mlp* actor, const nav_mlp* critic, const nav_replay* replay,
+                           int64_t size, int64_t B, const int64_t* idx, uint32_t seed_lo,
+                           uint32_t seed_hi, uint32_t counter, float* batch, float* q, float* da,
+                           float* acts, uint32_t save_mask, float* dz, uint32_t dz_save_mask,
+                           uint16_t* masks_actor, uint16_t* masks_critic, float* edge_slabs,
+                           ActorRowsArgs& a) {
     if (!actor || !critic || !replay || !replay->rows || B < 1 || size < 1 ||
         size > replay->capacity || size > ((int64_t)1 << 32) || !batch || !da ||
         (save_mask && !acts) || !masks_actor || !masks_critic || !edge_slabs ||
@@ -2785,7 +2734,137 @@ int nav_td3_actor_rows(const nav_mlp* actor, const nav_mlp* critic, const nav_re
     a.masks_c = masks_critic;
     a.eslab = edge_slabs;
     a.ecount = edge_count(a.actor);
-    return rows_dispatch(a.actor.hp, FAM_ACTOR, 0, 0, &a, 1, a.B, S(stream));
+    return 0;
+}
+
+// ---- the population learner's table and row launches ----
+// One member's CriticRowsArgs / ActorRowsArgs as TD3._critic_rows / _actor_rows pass them: the row
+// backward on, the middle hidden layers' rows saved for the weight gradients. `size` only has to
+// pass the check here (the launches carry the real one); no warmers.
+static int rows_member_fill(const nav_td3_member& t, int64_t B, CriticRowsArgs& c,
+                            ActorRowsArgs& a) {
+    const int nh = t.critics[0].n_hidden;
+    if (nh < 1 || nh >= kMaxLayers || t.actor.n_hidden != nh) return NAV_EINVAL;
+    uint32_t mid = 0;
+    for (int l = 1; l < nh - 1; ++l) mid |= 1u << l;
+    int rc = critic_rows_args(&t.target_actor, t.target_critics, t.critics, &t.replay, 1, B,
+                              t.idx_critic, t.seed_lo, t.seed_hi, 0u, t.eps, t.policy_noise,
+                              t.noise_clip, t.max_action, t.gamma, t.batch, t.dq, t.loss_part,
+                              t.edge_slabs, t.acts, mid, t.masks, 1, t.dz, mid, 0, c);
+    if (rc) return rc;
+    if (!t.edge_slabs[0] || !t.edge_slabs[1]) return NAV_EINVAL;  // the reduce reads them
+    rc = actor_rows_args(&t.actor, &t.critics[0], &t.replay, 1, B, t.idx_actor, t.seed_lo,
+                         t.seed_hi, 0u, t.batch_actor, t.q, t.da, t.acts_actor, mid, t.dz_actor,
+                         mid, t.masks_actor, t.masks[0], t.edge_slabs_actor, a);
+    return rc;
+}
+
+static bool same_net_shape(const nav_mlp& a, const nav_mlp& b) {
+    return a.d_in == b.d_in && a.d_out == b.d_out && a.hidden == b.hidden &&
+           a.hidden_pad == b.hidden_pad && a.n_hidden == b.n_hidden;
+}
+
+// The host-side check the population learner's row entry points share (before any HIP call);
+// crit / act (nullable): [n_members] host entries
+static int td3_pop_check(const nav_td3_member* members, int32_t n_members, int64_t B,
+                         CriticRowsArgs* crit, ActorRowsArgs* act) {
+    if (!members || n_members < 1 || n_members > kMaxMembers || B < 1) return NAV_EINVAL;
+    for (int m = 0; m < n_members; ++m) {
+        const nav_td3_member& t = members[m];
+        const nav_td3_member& t0 = members[0];
+        if (!same_net_shape(t.actor, t0.actor) || !same_net_shape(t.target_actor, t0.target_actor) ||
+            !same_net_shape(t.critics[0], t0.critics[0]) ||
+            !same_net_shape(t.critics[1], t0.critics[1]) ||
+            !same_net_shape(t.target_critics[0], t0.target_critics[0]) ||
+            !same_net_shape(t.target_critics[1], t0.target_critics[1]) ||
+            t.replay.capacity != t0.replay.capacity)
+            return NAV_EINVAL;
+        CriticRowsArgs c{};
+        ActorRowsArgs a{};
+        const int rc = rows_member_fill(t, B, c, a);
+        if (rc) return rc;
+        if (crit) crit[m] = c;
+        if (act) act[m] = a;
+    }
+    return 0;
+}
+
+int64_t nav_td3_pop_table_bytes(int32_t n_members) {
+    if (n_members < 1 || n_members > kMaxMembers) return NAV_EINVAL;
+    return (int64_t)n_members * (navi_rows_pop_entry_bytes() + navi_learner_pop_entry_bytes());
+}
+
+int nav_td3_pop_table_build(const nav_td3_member* members, int32_t n_members, int64_t B,
+                            int32_t splits_critic, int32_t splits_actor, void* table,
+                            void* stream) {
+    if (!table || n_members < 1 || n_members > kMaxMembers || splits_critic < 1 ||
+        splits_actor < 1)
+        return NAV_EINVAL;
+    const int64_t bytes = nav_td3_pop_table_bytes(n_members);
+    // the host image: [P] CriticRowsArgs | [P] ActorRowsArgs | [P] cross-row entries
+    uint32_t* host = static_cast<uint32_t*>(calloc((size_t)bytes / 4 + 1, 4));
+    if (!host) return NAV_EINVAL;
+    char* h = reinterpret_cast<char*>(host);
+    CriticRowsArgs* crit = reinterpret_cast<CriticRowsArgs*>(h);
+    ActorRowsArgs* act = reinterpret_cast<ActorRowsArgs*>(h + (size_t)n_members * sizeof(CriticRowsArgs));
+    int rc = td3_pop_check(members, n_members, B, crit, act);
+    if (!rc)
+        rc = navi_learner_pop_fill(members, n_members, B, splits_critic, splits_actor,
+                                   h + (size_t)n_members * navi_rows_pop_entry_bytes());
+    if (rc) {
+        free(host);
+        return rc;
+    }
+    constexpr int W = 512;  // 2 KB of kernel argument per write
+    const int64_t words = bytes / 4;
+    for (int64_t at = 0; at < words; at += W) {
+        TableChunk<W> c;
+        const int n = (int)(words - at < W ? words - at : W);
+        for (int i = 0; i < n; ++i) c.w[i] = host[at + i];
+        hipLaunchKernelGGL(k_table_chunk_write<W>, dim3(1), dim3(256), 0, S(stream), c,
+                           static_cast<uint32_t*>(table) + at, n);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            free(host);
+            return -(int)e;
+        }
+    }
+    free(host);
+    return 0;
+}
+
+static int rows_pop_launch(const nav_td3_member* members, int32_t n_members, int64_t B,
+                           const void* table, int64_t size, uint32_t counter, int32_t split_twins,
+                           int fam, void* stream) {
+    if (!table) return NAV_EINVAL;
+    const int rc = td3_pop_check(members, n_members, B, nullptr, nullptr);
+    if (rc) return rc;
+    if (size < 1 || size > members[0].replay.capacity || size > ((int64_t)1 << 32))
+        return NAV_EINVAL;
+    RowsPopLaunch a{};
+    const char* t = static_cast<const char*>(table);
+    a.k.table = fam == FAM_CRITIC_POP ? t : t + (size_t)n_members * sizeof(CriticRowsArgs);
+    a.k.size = size;
+    a.k.counter = counter;
+    a.k.split_twins = split_twins;
+    a.B = B;
+    a.n_hidden = members[0].critics[0].n_hidden;
+    a.n_members = n_members;
+    return rows_dispatch(members[0].actor.hidden_pad, fam, 0, 0, &a, 1, B, S(stream));
+}
+
+int nav_td3_critic_rows_pop(const nav_td3_member* members, int32_t n_members, int64_t B,
+                            const void* table, int64_t size, uint32_t counter,
+                            int32_t split_twins, void* stream) {
+    // the twins in separate workgroups while all members' rows leave CUs idle, as
+    // nav_td3_critic_rows chooses for one member
+    const int tw = split_twins < 0 ? ((int64_t)n_members * B <= 2048 ? 1 : 0) : (split_twins ? 1 : 0);
+    return rows_pop_launch(members, n_members, B, table, size, counter, tw, FAM_CRITIC_POP, stream);
+}
+
+int nav_td3_actor_rows_pop(const nav_td3_member* members, int32_t n_members, int64_t B,
+                           const void* table, int64_t size, uint32_t counter, void* stream) {
+    return rows_pop_launch(members, n_members, B, table, size, counter, 0, FAM_ACTOR_POP, stream);
 }
 
 int64_t nav_mlp_mask_count(int32_t hidden_pad, int32_t n_hidden, int64_t M) {

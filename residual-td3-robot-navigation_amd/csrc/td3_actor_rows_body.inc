@@ -1,0 +1,98 @@
+// k_td3_actor_rows' statements (mlp_kernels.hip includes this once per form, as
+// td3_critic_rows_body.inc)
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    if constexpr (!POP) {
+        if (a.warm.n && (int)blockIdx.y >= a.warm.y0) {  // an L2 warmer row (small grids)
+            warm_l2(a.warm);
+            return;
+        }
+    }
+    constexpr int hp = NT * 32, SS = hp + 4, TM = RT * 32;
+    const int tid = threadIdx.x;
+    const int64_t B = a.B, row0 = (int64_t)blockIdx.x * TM, rt0 = (int64_t)blockIdx.x * RT;
+    const int64_t n_rt = mask_rowtiles(B);
+    float* act = smem;
+    float* xin = act + TM * SS;      // [TM][4] (s, pi(s))
+    float* red = xin + TM * 4;       // [2][PARTS][TM]
+    float* dys = red + red_floats(TM);  // [TM][4] critic dy
+    float* dys2 = dys + TM * 4;      // [TM][4] actor dy = dL/da
+    _Float16* stage = reinterpret_cast<_Float16*>(dys2 + TM * 4);  // gemm_cols' split stage
+    const L0Pre l0_a = load_l0<NT>(a.actor);  // in flight under the sampling
+    NAV_CLOCK(1, 0);
+    if (tid < TM) {
+        const int64_t b = row0 + tid;
+        float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+        if (b < B) {
+            if constexpr (POP)
+                sample_row(a.rows, pv.size, a.idx, a.seed_lo, a.seed_hi, 2u * pv.counter + 1u, b,
+                           lo, hi);
+            else
+                sample_row(a.rows, a.rsize, a.idx, a.seed_lo, a.seed_hi, a.sample_ctr, b, lo, hi);
+            float4* dst = reinterpret_cast<float4*>(a.batch) + 2 * b;
+            dst[0] = lo;
+            dst[1] = hi;
+        }
+        *reinterpret_cast<float4*>(xin + tid * 4) = make_float4(lo.x, lo.y, 0.f, 0.f);  // s
+        *reinterpret_cast<float4*>(dys + tid * 4) =
+            make_float4(b < B ? a.dq : 0.f, 0.f, 0.f, 0.f);
+    }
+    __syncthreads();
+    // the actor's top hidden layer stays in registers until dL/da is known (its dWo partials)
+    f32x16 topa[RT][2];
+    fwd_net<NT, RT, 1, 2>(a.actor, act, stage, xin, red, a.masks_a, n_rt, a.acts, a.save_mask, row0, B, rt0,
+                    topa, -64, &l0_a);
+    const L0Pre l0_c = load_l0<NT>(a.critic);  // in flight under the action epilogue
+    if (tid < 2 * TM) {
+        const int rloc = tid % TM, j = tid / TM;
+        xin[rloc * 4 + 2 + j] = row0 + rloc < B ? out_y<RT>(a.actor, red, rloc, j) : 0.f;
+    }
+    __syncthreads();
+    // the critic's top-layer ReLU bits and Wo columns go from its forward to its row backward in
+    // registers (as in critic_rows)
+    f32x16 top[RT][2];
+    uint32_t top_bits[RT * 2];
+    WoCols wo;
+    fwd_net<NT, RT, 1, 4>(a.critic, act, stage, xin, red, a.masks_c, n_rt, nullptr, 0u, row0, B, rt0, top,
+                    -64, &l0_c, top_bits, &wo);
+    // One hidden layer (CBM == 0): fwd_net's top layer is layer 0 and it leaves top_bits unset;
+    // the row backward below read them uninitialised (the one-hidden-layer learner did not repeat
+    // its own results). The bits are those of `top`, layer 0's post-ReLU registers.
+    if constexpr (CBM == 0) {
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                uint32_t bits = 0;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) bits |= pos_bit(top[rt][j][i]) << i;
+                top_bits[rt * 2 + j] = bits;
+            }
+    }
+    if (tid < TM && a.q && row0 + tid < B) a.q[row0 + tid] = out_y<RT>(a.critic, red, tid, 0);
+    bwd_net<NT, RT, 1, CBM>(a.critic, act, stage, dys, xin, a.masks_c, n_rt, nullptr, nullptr,
+                                    nullptr, 0u, row0, B, rt0, -64, top_bits, &wo);
+    if (tid < 2 * TM) {
+        const int rloc = tid % TM, j = tid / TM;
+        const int64_t r = row0 + rloc;
+        const float v = r < B ? dx_unit<NT>(a.critic, act, rloc, 2 + j) : 0.f;
+        dys2[rloc * 4 + j] = v;
+        if (r < B) a.da[r * 2 + j] = v;
+    }
+    if (tid < TM) {
+        dys2[tid * 4 + 2] = 0.f;
+        dys2[tid * 4 + 3] = 0.f;
+    }
+    __syncthreads();
+    // the actor's output layer gradient partials: dWo from its top-layer registers, dbo = column
+    // sums of dL/da (bwd_net's order)
+    float* es = a.eslab + (int64_t)blockIdx.x * a.ecount;
+    wo_grad_regs<NT, RT>(a.actor, topa, dys2, 4, es);
+    if (tid < 4) {
+        float sb = 0.f;
+        if (tid < a.actor.d_out)
+            for (int rr = 0; rr < TM; ++rr) sb += dys2[rr * 4 + tid];
+        es[e_bo(a.actor) + tid] = sb;
+    }
+    bwd_net<NT, RT>(a.actor, act, stage, dys2, xin, a.masks_a, n_rt, es, nullptr, a.dz, a.dz_save_mask,
+                    row0, B, rt0, -64, nullptr, nullptr, false);
+    NAV_CLOCK(1, 1);

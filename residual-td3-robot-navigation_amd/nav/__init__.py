@@ -9,7 +9,7 @@ libnavenv.so (C-ABI: include/navenv.h), with the reference's Python API on top.
 from . import config  # noqa: F401
 
 __all__ = ["Environment", "Robot", "VecEnv", "VecTrainer", "TD3", "DeviceMLP", "ReplayRing",
-           "PopulationTrainer", "PopulationTable", "sweep_grid"]
+           "PopulationTrainer", "PopulationTable", "PopulationLearner", "sweep_grid"]
 
 
 def __getattr__(name):
@@ -20,7 +20,7 @@ def __getattr__(name):
     if name == "VecTrainer":
         from .trainer import VecTrainer
         return VecTrainer
-    if name in ("PopulationTrainer", "PopulationTable", "sweep_grid"):
+    if name in ("PopulationTrainer", "PopulationTable", "PopulationLearner", "sweep_grid"):
         from . import population
         return getattr(population, name)
     if name == "TD3":

@@ -58,6 +58,26 @@ class NavTestOut(C.Structure):
                 ("traj", _vp)]
 
 
+class NavTd3Member(C.Structure):
+    """nav_td3_member: one member of the population learner (its networks, ring, moments,
+    hyper-parameters, injected samples and workspace)."""
+    _fields_ = [
+        ("actor", NavMlp), ("critics", NavMlp * 2), ("target_actor", NavMlp),
+        ("target_critics", NavMlp * 2), ("replay", NavReplay),
+        ("m_actor", _vp), ("v_actor", _vp), ("m_critic", _vp * 2), ("v_critic", _vp * 2),
+        ("actor_lr", C.c_double), ("critic_lr", C.c_double),
+        ("policy_noise", C.c_float), ("noise_clip", C.c_float), ("max_action", C.c_float),
+        ("gamma", C.c_float), ("tau", C.c_float),
+        ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32),
+        ("idx_critic", _vp), ("idx_actor", _vp), ("eps", _vp),
+        ("batch", _vp), ("batch_actor", _vp), ("dq", _vp * 2), ("loss_part", _vp * 2),
+        ("edge_slabs", _vp * 2), ("edge_slabs_actor", _vp), ("acts", _vp * 2),
+        ("acts_actor", _vp), ("dz", _vp * 2), ("dz_actor", _vp), ("masks", _vp * 2),
+        ("masks_actor", _vp), ("q", _vp), ("da", _vp), ("hidden_slabs", _vp * 2),
+        ("grad_critic", _vp * 2), ("grad_actor", _vp),
+    ]
+
+
 # (name, restype, argtypes) for every entry point of include/navenv.h
 _P = C.POINTER
 SIGNATURES = [
@@ -177,6 +197,20 @@ SIGNATURES = [
     ("nav_fill", C.c_int, [_vp, C.c_int64, C.c_float, _vp]),
     ("nav_strided_copy", C.c_int, [_vp, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32,
                                    C.c_int64, C.c_int32, _vp]),
+    ("nav_td3_pop_table_bytes", C.c_int64, [C.c_int32]),
+    ("nav_td3_pop_table_build", C.c_int, [_P(NavTd3Member), C.c_int32, C.c_int64, C.c_int32,
+                                          C.c_int32, _vp, _vp]),
+    ("nav_td3_critic_rows_pop", C.c_int, [_P(NavTd3Member), C.c_int32, C.c_int64, _vp, C.c_int64,
+                                          C.c_uint32, C.c_int32, _vp]),
+    ("nav_td3_actor_rows_pop", C.c_int, [_P(NavTd3Member), C.c_int32, C.c_int64, _vp, C.c_int64,
+                                         C.c_uint32, _vp]),
+    ("nav_mlp_wgrad_splits_pop", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_int64]),
+    ("nav_mlp_wgrad_pop", C.c_int, [_P(NavTd3Member), C.c_int32, C.c_int64, _vp, C.c_int32,
+                                    C.c_int32, _vp]),
+    ("nav_grad_reduce_adam_pop", C.c_int, [_P(NavTd3Member), C.c_int32, C.c_int64, _vp,
+                                           C.c_int32, C.c_float, C.c_float, C.c_float,
+                                           C.c_double, C.c_float, C.c_int32, _vp]),
     ("nav_event_create", C.c_int, [_P(_vp)]),
     ("nav_event_destroy", C.c_int, [_vp]),
     ("nav_event_record", C.c_int, [_vp, _vp]),
@@ -186,7 +220,8 @@ SIGNATURES = [
 # Entry points that return int64 counts (negative = error) rather than a status code.
 _COUNT_FNS = {"nav_mlp_param_count", "nav_mlp_packed_count", "nav_mlp_mask_count",
               "nav_mlp_row_blocks", "nav_mlp_edge_count", "nav_mlp_hidden_count",
-              "nav_mlp_wgrad_splits", "nav_demo_index_res", "nav_pop_table_bytes"}
+              "nav_mlp_wgrad_splits", "nav_demo_index_res", "nav_pop_table_bytes",
+              "nav_td3_pop_table_bytes", "nav_mlp_wgrad_splits_pop"}
 
 
 class NavError(RuntimeError):

@@ -6,18 +6,28 @@ The reference's only published result is a hyper-parameter study (the score over
 DEMO_PROXIMITY_FACTOR in {10, 30, 50, 70}; simulator.py:169-200 attempts the same over
 INITIAL_NOISE x NOISE_DECAY). Envs are independent of each other (environment.py:98-137), so a
 sweep is a population: member m owns the consecutive envs [m * envs_per_member, (m + 1) *
-envs_per_member) and ends exactly as it would alone on the whole env set, bit for bit. The
-learner's row kernels are not batched over members: each member's td3_update runs today's kernels
-at its batch size, optionally round-robin over a few streams.
+envs_per_member) and ends exactly as it would alone on the whole env set, bit for bit.
+
+The learner has two forms. learner="members" (the default): each member's td3_update runs the
+single-member kernels at its batch size, optionally round-robin over a few streams.
+learner="batched" (PopulationLearner): every member's TD3 epoch in one launch per kernel
+(nav_td3_critic_rows_pop, nav_mlp_wgrad_pop, nav_grad_reduce_adam_pop, nav_td3_actor_rows_pop):
+the same kernels with a member dimension on the grid, member m's arguments read from a device
+table built once, the replay fill, the Philox counter and Adam's bias corrections by value. Member
+m ends bit for bit as its own td3_update with the same weight-gradient split counts; those are
+chosen to fill the chip with all members' tiles, so for P > 1 they differ from a lone learner's
+(wgrad_splits= sets up a "members" run to match).
 """
 import ctypes as C
 import dataclasses
 import itertools
+import math
 
 import torch
 
 from . import config as K
-from ._lib import NavMlp, NavParams, NavReplay, lib, params_struct, ptr, stream_handle
+from ._lib import (NavMlp, NavParams, NavReplay, NavTd3Member, lib, params_struct, ptr,
+                   stream_handle)
 from .cem import cem_group_demo_sets
 from .fields import make_field_device
 from .td3 import TD3
@@ -82,6 +92,162 @@ class PopulationTable:
                                   self.envs_per_member, ptr(self.table), stream_handle(stream))
 
 
+class PopulationLearner:
+    """Every member's TD3 epoch (robot.py:258-285) in one launch per kernel. Built from the
+    members' TD3 objects and rings; it owns no network: each TD3 stays the owner of its networks,
+    moments and workspace (state_dict(), critic_loss_values() and checkpoints work per member as
+    before), this class holds the device table of their kernel arguments and issues the launches.
+
+    The members must agree on what the launches share: network shape, batch size,
+    policy_update_delay, update_counter, the optimizers' step counts, betas and eps, and ring
+    capacity and fill. Everything else (weights, seed, learning rates, gamma, tau, policy_noise,
+    noise_clip, max_action) is the member's own. Call rebuild() after changing a member's
+    hyper-parameter (cfg or an optimizer's lr) or replacing one of its buffers."""
+
+    def __init__(self, td3, rings, stream=None):
+        self.td3, self.rings = list(td3), list(rings)
+        P = self.P = len(self.td3)
+        if P < 1 or len(self.rings) != P:
+            raise ValueError("a population learner needs one ring per TD3, at least one")
+        t0 = self.td3[0]
+        for t in self.td3:
+            if t.grad_hook is not None:
+                raise ValueError("PopulationLearner: a TD3 with a grad_hook (shared policy) "
+                                 "takes the per-member path")
+            if (t.cfg.batch_size, t.cfg.net) != (t0.cfg.batch_size, t0.cfg.net):
+                raise ValueError("PopulationLearner: one batch size and network shape")
+        self._check_schedule()
+        self.B = int(t0.cfg.batch_size)
+        self.wgrad_splits = self.split_counts(P, t0.cfg.net.hidden, t0.cfg.net.n_hidden, self.B)
+        # the twin online critics in separate workgroups: -1 = the library's choice from all
+        # members' rows (1 / 0 force either form; the results are bit-identical)
+        self.split_twins = -1
+        self._inject = [(None, None, None)] * P
+        self.table = torch.zeros(lib().nav_td3_pop_table_bytes(P), dtype=torch.uint8,
+                                 device=t0.device)
+        self.rebuild(stream)
+
+    @staticmethod
+    def split_counts(n_members, hidden, n_hidden, batch):
+        """(critic twins, actor) row splits of the weight-gradient launches that fill the chip
+        with all members' tile jobs (nav_mlp_wgrad_splits_pop), as TD3's wgrad_splits= takes
+        them."""
+        hp = (int(hidden) + 31) // 32 * 32
+        L = lib()
+        sc = L.nav_mlp_wgrad_splits_pop(n_members, 2, 1, hp, n_hidden, batch)
+        sa = L.nav_mlp_wgrad_splits_pop(n_members, 1, 2, hp, n_hidden, batch)
+        return tuple(max(1, min(int(v), max(1, int(batch) // 32))) for v in (sc, sa))
+
+    def _opts(self, t):
+        return (t.critic_optimizer_1, t.critic_optimizer_2, t.actor_optimizer)
+
+    def _check_schedule(self):
+        t0 = self.td3[0]
+        key = lambda t: (t.cfg.policy_update_delay, t.update_counter,  # noqa: E731
+                         tuple((o.step_count, o.b1, o.b2, o.eps) for o in self._opts(t)))
+        if any(key(t) != key(t0) for t in self.td3):
+            raise ValueError("PopulationLearner: the members' policy_update_delay, update_counter "
+                             "and optimizer step counts (and betas, eps) must be equal")
+        c1, c2, _ = self._opts(t0)
+        if (c1.step_count, c1.b1, c1.b2, c1.eps) != (c2.step_count, c2.b1, c2.b2, c2.eps):
+            raise ValueError("PopulationLearner: the twin critics' optimizers must be in step")
+        for t in self.td3:
+            if t.critic_optimizer_1.lr != t.critic_optimizer_2.lr:
+                raise ValueError("PopulationLearner: one learning rate for a member's twins")
+
+    def inject(self, idx_critic=None, idx_actor=None, eps=None, stream=None):
+        """Per member (lists of P tensors, or None): the critic batch's and the actor batch's
+        sample indices (int64 [B]) and the target-smoothing noise (float32 [B][2]) that every
+        later epoch uses instead of its Philox draws, as td3_update's idx_fn / eps_fn. The table
+        holds the pointers: the tensors are kept alive here and may be refilled in place."""
+        pick = lambda v, m: None if v is None else v[m]  # noqa: E731
+        self._inject = [(pick(idx_critic, m), pick(idx_actor, m), pick(eps, m))
+                        for m in range(self.P)]
+        self.rebuild(stream)
+
+    def _member(self, t, ring, inj):
+        c = t.cfg
+        m = NavTd3Member()
+        m.actor, m.target_actor = t.actor_network.desc(), t.target_actor.desc()
+        m.critics[0], m.critics[1] = t.critic_network_1.desc(), t.critic_network_2.desc()
+        m.target_critics[0] = t.target_critic_network_1.desc()
+        m.target_critics[1] = t.target_critic_network_2.desc()
+        m.replay = ring.desc()
+        oc1, oc2, oa = self._opts(t)
+        m.m_actor, m.v_actor = oa.m.data_ptr(), oa.v.data_ptr()
+        m.m_critic[0], m.m_critic[1] = oc1.m.data_ptr(), oc2.m.data_ptr()
+        m.v_critic[0], m.v_critic[1] = oc1.v.data_ptr(), oc2.v.data_ptr()
+        m.actor_lr, m.critic_lr = oa.lr, oc1.lr
+        m.policy_noise, m.noise_clip, m.max_action = c.policy_noise, c.noise_clip, c.max_action
+        m.gamma, m.tau = c.gamma, c.tau
+        m.seed_lo, m.seed_hi = t.seed & 0xFFFFFFFF, (t.seed >> 32) & 0xFFFFFFFF
+        dp = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        m.idx_critic, m.idx_actor, m.eps = (dp(x) for x in inj)
+        m.batch, m.batch_actor = t.batch.data_ptr(), t.batch2.data_ptr()
+        for i, (dq, lp, es, ac, dz, mk, hs, g) in enumerate((
+                (t.dq1, t.loss_part[0], t.eslab1, t.acts1, t.dz1, t.mask1, t.hslab, t.grad_c1),
+                (t.dq2, t.loss_part[1], t.eslab2, t.acts2, t.dz2, t.mask2, t.hslab2, t.grad_c2))):
+            m.dq[i], m.loss_part[i], m.edge_slabs[i] = dq.data_ptr(), lp.data_ptr(), es.data_ptr()
+            m.acts[i], m.dz[i], m.masks[i] = ac.data_ptr(), dz.data_ptr(), mk.data_ptr()
+            m.hidden_slabs[i], m.grad_critic[i] = hs.data_ptr(), g.data_ptr()
+        m.edge_slabs_actor, m.acts_actor = t.eslab_a.data_ptr(), t.acts_a.data_ptr()
+        m.dz_actor, m.masks_actor = t.dz_a.data_ptr(), t.mask_a.data_ptr()
+        m.q, m.da, m.grad_actor = t.q1.data_ptr(), t.da.data_ptr(), t.grad_a.data_ptr()
+        return m
+
+    def rebuild(self, stream=None):
+        """(Re)build the device table from the members' present buffers and hyper-parameters; each
+        member's workspace is (re)allocated for the population's split counts first."""
+        self._check_schedule()
+        for t in self.td3:
+            if t._B != self.B or (t.splits_c, t.splits_a) != self.wgrad_splits:
+                t.wgrad_splits = self.wgrad_splits
+                t._B = 0
+                t._workspace(self.B)
+        self.members = (NavTd3Member * self.P)(*[
+            self._member(t, r, j) for t, r, j in zip(self.td3, self.rings, self._inject)])
+        lib().nav_td3_pop_table_build(self.members, self.P, self.B, self.wgrad_splits[0],
+                                      self.wgrad_splits[1], ptr(self.table),
+                                      stream_handle(stream))
+
+    def _step(self, group, soft_update, s):
+        """The group's weight gradients, then reduce + Adam (+ the soft updates) and the packed
+        images: every member's optimizer advances as _Adam.advance() does."""
+        L = lib()
+        L.nav_mlp_wgrad_pop(self.members, self.P, self.B, ptr(self.table), group,
+                            self.wgrad_splits[group], s)
+        for t in self.td3:
+            for o in (self._opts(t)[:2] if group == 0 else self._opts(t)[2:]):
+                o.step_count += 1
+        o = self._opts(self.td3[0])[0 if group == 0 else 2]
+        bc1 = 1 - o.b1 ** o.step_count
+        bc2 = 1 - o.b2 ** o.step_count
+        L.nav_grad_reduce_adam_pop(self.members, self.P, self.B, ptr(self.table), group, o.b1,
+                                   o.b2, o.eps, bc1, math.sqrt(bc2), int(soft_update), s)
+
+    def update(self, num_epochs=None, stream=None):
+        """TD3._update's schedule for every member at once: the critic phase every epoch, the
+        actor phase with the three soft updates on epoch % policy_update_delay == 0."""
+        t0 = self.td3[0]
+        n = t0.cfg.num_epochs if num_epochs is None else num_epochs
+        size = len(self.rings[0])
+        if any(len(r) != size for r in self.rings):
+            raise ValueError("PopulationLearner: the rings must be filled alike")
+        if size < 1:
+            return
+        L, s, tab = lib(), stream_handle(stream), ptr(self.table)
+        for epoch in range(n):
+            ctr = t0.update_counter
+            L.nav_td3_critic_rows_pop(self.members, self.P, self.B, tab, size, ctr,
+                                      self.split_twins, s)
+            self._step(0, False, s)
+            if epoch % t0.cfg.policy_update_delay == 0:
+                L.nav_td3_actor_rows_pop(self.members, self.P, self.B, tab, size, ctr, s)
+                self._step(1, True, s)
+            for t in self.td3:
+                t.update_counter += 1
+
+
 class PopulationTrainer:
     """VecTrainer for P members at once. `members` is a list of dicts of overrides: fields of
     `nav_params` go to the member's constants (`path_length0` also fills the member's slice of
@@ -91,13 +257,19 @@ class PopulationTrainer:
 
     def __init__(self, members, envs_per_member=4096, hidden=256, n_hidden=2, batch=4096,
                  updates_per_step=2, seed=K.RANDOM_SEED, envs_per_group=1024, demos=True,
-                 streams=1, replay_capacity=None, device="cuda", field=None):
+                 streams=1, replay_capacity=None, device="cuda", field=None, learner="members",
+                 wgrad_splits=None):
         self.members = [dict(m) for m in members]
         P = self.P = len(self.members)
         if P < 1:
             raise ValueError("a population needs at least one member")
         if not 1 <= int(streams) <= 4:
             raise ValueError("streams must be 1 .. 4")
+        if learner not in ("members", "batched"):
+            raise ValueError('learner must be "members" or "batched"')
+        if learner == "batched" and int(streams) != 1:
+            raise ValueError('learner="batched" issues one launch for all members: streams must '
+                             'be 1')
         routed = [route_overrides(m) for m in self.members]
         self.epm = int(envs_per_member)
         self.n = P * self.epm
@@ -122,10 +294,16 @@ class PopulationTrainer:
         self.ring_rows = torch.zeros(P, cap, 8, dtype=torch.float32, device=self.device)
         self.rings = [ReplayRing(cap, self.device, rows=self.ring_rows[m]) for m in range(P)]
         self.td3 = []
+        # the weight-gradient row splits: the batched learner's fill the chip with all members'
+        # tiles; "members" takes TD3's own unless wgrad_splits= asks for others (to match a
+        # batched run bit for bit)
+        if learner == "batched":
+            wgrad_splits = PopulationLearner.split_counts(P, hidden, n_hidden, int(batch))
         for m, (pk, ck, ex) in enumerate(routed):
             cfg = K.TD3Config(batch_size=int(batch), num_epochs=int(updates_per_step),
                               net=K.NetConfig(hidden=hidden, n_hidden=n_hidden), **ck)
-            t = TD3(cfg, device=self.device, seed=int(ex.get("seed", self.seed)))
+            t = TD3(cfg, device=self.device, seed=int(ex.get("seed", self.seed)),
+                    wgrad_splits=wgrad_splits)
             t._workspace(cfg.batch_size)  # allocated now, on the stream every later one waits for
             self.td3.append(t)
             sl = self.member_slice(m)
@@ -140,6 +318,7 @@ class PopulationTrainer:
         self.updates_per_step = int(updates_per_step)
         self.streams = int(streams)
         self._side = None
+        self.learner = PopulationLearner(self.td3, self.rings) if learner == "batched" else None
 
     def member_slice(self, m):
         return slice(m * self.epm, (m + 1) * self.epm)
@@ -160,7 +339,14 @@ class PopulationTrainer:
     def learn(self, stream=None):
         """Each member's td3_update on its own ring. streams > 1: the members go round-robin over
         that many side streams, which start after the tick and are joined before this returns
-        control of `stream` (the members share nothing, so the results do not depend on it)."""
+        control of `stream` (the members share nothing, so the results do not depend on it).
+        learner="batched": every member's epochs in one launch per kernel (PopulationLearner),
+        once every ring holds a batch."""
+        if self.learner is not None:
+            if (self.updates_per_step > 0 and
+                    all(len(r) >= self.learner.B for r in self.rings)):
+                self.learner.update(self.updates_per_step, stream)
+            return
         if self.streams == 1:
             for m in range(self.P):
                 self._learn_member(m, stream)

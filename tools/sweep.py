@@ -69,6 +69,9 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=None, help="default: envs per member")
     ap.add_argument("--updates-per-step", type=int, default=2)
     ap.add_argument("--streams", type=int, default=1)
+    ap.add_argument("--learner", choices=("members", "batched"), default="members",
+                    help="batched: every member's TD3 epoch in one launch per kernel "
+                         "(needs --streams 1)")
     ap.add_argument("--test-steps", type=int, default=K.TEST_TIMEOUT * K.UPDATE_RATE)
     ap.add_argument("--seed", type=int, default=K.RANDOM_SEED)
     ap.add_argument("--no-demos", action="store_true")
@@ -87,7 +90,7 @@ def main(argv=None):
                            n_hidden=a.n_hidden, batch=a.batch or a.envs_per_member,
                            updates_per_step=a.updates_per_step, seed=a.seed,
                            envs_per_group=min(a.envs_per_group, a.envs_per_member),
-                           demos=not a.no_demos, streams=a.streams)
+                           demos=not a.no_demos, streams=a.streams, learner=a.learner)
     for _ in range(a.train_steps):
         tr.step()
     for m, row in enumerate(tr.evaluate(max_steps=a.test_steps)):
