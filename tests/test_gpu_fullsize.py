@@ -301,7 +301,7 @@ def test_learner_gradients_at_bench_config_vs_oracle():
     a uniform gradient-scale error (a wrong 2/B, -1/B or split count); this does. The oracle uses
     the kernels' own ReLU decisions (pre-activations within rounding of 0 may branch either way).
     Every entry within rtol 1e-4; scale <g, g_ref> / |g_ref|^2 within 1e-5 of 1 per net."""
-    from test_gpu_mlp import relu_bits
+    from mlp_ref import relu_bits
     from test_gpu_shared_policy import make_learner, replay_rows, ring_of
     from oracle.td3_oracle import TD3Oracle, make_mlp_params
     B, hidden, nh = 32768, 256, 2

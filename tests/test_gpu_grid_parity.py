@@ -57,7 +57,7 @@ def test_row_kernels_vs_fp64_every_band_occupied(nav, d_in, d_out, hidden, nh):
     out 3.2e-7 / 3.4e-7 / 6.2e-7, h 1.0e-7 .. 5.3e-7, dz 4.2e-8 .. 3.7e-7, dx 4.7e-7 / 3.8e-7 /
     3.6e-7 of scale (fp32 itself ~1e-7), dW 8.3e-7 / 5.9e-7 / 6.8e-7; no band stands out."""
     from nav._lib import lib
-    from test_gpu_mlp import split_gemm_row_errors
+    from mlp_ref import split_gemm_row_errors
     M = 65505
     assert lib().nav_mlp_row_blocks(M) == 1024
     rows, dW = split_gemm_row_errors(d_in, d_out, hidden, nh, M)
@@ -76,7 +76,7 @@ def acting(nav):
     step 7, and the fp64 forward of f32(state - goal)."""
     from nav._lib import lib, params_struct, ptr, stream_handle
     from nav.vec_env import VecEnv, make_field
-    from test_gpu_mlp import _f64_forward, make_net
+    from mlp_ref import _f64_forward, make_net
     t = golden("trace.npz")
     n, step = 65536, 7
     env = VecEnv(n, make_field(t["speed"], t["angle"], DEV), seed=SEED, envs_per_group=1024)

@@ -16,9 +16,10 @@ import pytest
 import torch
 
 from conftest import golden
+from mlp_ref import (DEV, _assert_images_exact, _f64_forward, _grad_flat_vs_autograd,  # noqa: F401
+                     make_net, relu_bits, split_gemm_row_errors, torch_mlp)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 
 
 @pytest.fixture(scope="module")
@@ -28,23 +29,6 @@ def nav():
     _lib.lib()
     import nav as navpkg
     return navpkg
-
-
-def torch_mlp(layers, x):
-    h = x
-    for i, (W, b) in enumerate(layers):
-        h = torch.nn.functional.linear(h, W, b)
-        if i < len(layers) - 1:
-            h = torch.relu(h)
-    return h
-
-
-def make_net(d_in, d_out, hidden, nh, seed):
-    from nav.mlp import DeviceMLP
-    from oracle.td3_oracle import make_mlp_params
-    p = make_mlp_params(seed, [d_in] + [hidden] * nh + [d_out])
-    net = DeviceMLP(d_in, d_out, hidden, nh, DEV).load(p)
-    return net, [(torch.tensor(W), torch.tensor(b)) for W, b in p]
 
 
 @pytest.mark.parametrize("d_in,d_out,hidden,nh", [(2, 2, 200, 3), (4, 1, 200, 3), (2, 2, 256, 2),
@@ -154,34 +138,6 @@ def test_act_vs_reference_golden(nav, orc):
     lib().nav_act(C.byref(p), C.byref(d), n, ptr(st), ptr(gl), None, None, 0, 1, ptr(act),
                   None, stream_handle())
     assert np.allclose(act.cpu().numpy(), g["action_test"], rtol=0, atol=2e-4)
-
-
-def _grad_flat_vs_autograd(net, tl, gflat, d_in, d_out, nh):
-    from nav.mlp import layer_offsets
-    offs, _ = layer_offsets(d_in, d_out, net.hp, nh)
-    for l, ((W, b), (w_off, b_off, fo, fi)) in enumerate(zip(tl, offs)):
-        o, i = W.shape
-        gW = gflat[w_off:w_off + fo * fi].view(fo, fi)
-        tol = 1e-5 * (W.grad.abs().max() + 1e-6)
-        assert torch.allclose(gW[:o, :i], W.grad, rtol=1e-3, atol=tol), l
-        assert (gW[o:, :] == 0).all() and (gW[:, i:] == 0).all()
-        gb = gflat[b_off:b_off + o]
-        assert torch.allclose(gb, b.grad, rtol=1e-3, atol=1e-5 * (b.grad.abs().max() + 1e-6)), l
-        assert (gflat[b_off + o:b_off + fo] == 0).all()
-
-
-def relu_bits(masks, nh, hp, hidden, M):
-    """The forward's ReLU bit image ([nh][M / 32 row tiles][hp / 32][64 lanes] u16 words, C
-    layout: bit i of lane (l32, h) = row (i & 3) + 8 (i >> 2) + 4 h of the tile, column l32) as
-    [nh][M][hidden] booleans."""
-    nt = hp // 32
-    w = masks.cpu().to(torch.int32) & 0xFFFF
-    n_rt = w.numel() // (nh * nt * 64)
-    bits = ((w.view(nh, n_rt, nt, 2, 32, 1) >> torch.arange(16)) & 1).bool()
-    r = torch.arange(32)
-    hh, ii = (r >> 2) & 1, (r & 3) + 4 * (r >> 3)  # lane half and element of tile row r
-    b = bits.permute(0, 1, 3, 5, 2, 4)[:, :, hh, ii]  # [nh][n_rt][32 rows][nt][32 cols]
-    return b.reshape(nh, n_rt * 32, nt * 32)[:, :M, :hidden]
 
 
 @pytest.mark.parametrize("d_in,d_out,hidden,nh,M", [(4, 1, 200, 3, 100), (2, 2, 200, 3, 777),
@@ -661,7 +617,8 @@ def test_reduce_adam_polyak_fused_bitwise(nav):
             assert torch.equal(x.params, y.params) and torch.equal(x.packed, y.packed)
 
 
-@pytest.mark.parametrize("hidden,nh", [(256, 2), (200, 3), (96, 4), (64, 1)])
+@pytest.mark.parametrize("hidden,nh", [(256, 2), (200, 3), (96, 4), (64, 1), (24, 2), (128, 3),
+                                       (150, 2), (192, 1)])
 @pytest.mark.parametrize("M", [1, 1000, 20000])
 def test_acting_forward_residual_bitwise(nav, hidden, nh, M):
     """nav_act's residual (the acting forward, robot.py:556, 598-624: input rows f32(state - goal)
@@ -685,19 +642,6 @@ def test_acting_forward_residual_bitwise(nav, hidden, nh, M):
 
 
 # ---- fp32 accuracy of the split GEMMs (the property behind the bench's "fp32" dtype) ----
-def _f64_forward(layers, x):
-    """fp64 forward of the same f32 weights; returns the output and every hidden pre-activation."""
-    h, zs = x.double(), []
-    for i, (W, b) in enumerate(layers):
-        z = torch.nn.functional.linear(h, W.double(), b.double())
-        if i < len(layers) - 1:
-            zs.append(z)
-            h = torch.relu(z)
-        else:
-            h = z
-    return h, zs
-
-
 @pytest.mark.parametrize("M", [4096, 16421])
 def test_split_gemm_per_row_accuracy_rows_spanning_binades(nav, M):
     """Per-row accuracy of the split GEMM's A operand: the A scale is per 32-row
@@ -737,73 +681,6 @@ def test_split_gemm_per_row_accuracy_rows_spanning_binades(nav, M):
     assert bool((err[live] <= bound[live]).all()), float((err[live] / bound[live]).max())
     print("per-row err: max %.2e, median %.2e; rows with s > 12: max %.2e" % (
         err[live].max(), err[live].median(), err[live & (s > 12)].max()))
-
-
-def split_gemm_row_errors(d_in, d_out, hidden, nh, M):
-    """The launches and the fp64 reference of test_split_gemm_f32_accuracy_vs_fp64 at M rows.
-    Returns (rows, dW): rows[name] = (|err| per row [M] (the row's worst entry), max |ref|) for
-    the output, every saved activation h_l, every dz_l and dx; dW[name] = max |err| / max |ref|
-    of every hidden x hidden weight gradient. Asserts on the way that the forward's ReLU bits
-    equal the fp64 signs outside the rounding band."""
-    from nav._lib import descs, lib, parr, ptr, stream_handle
-    from nav.mlp import forward
-    net, layers = make_net(d_in, d_out, hidden, nh, 17)
-    g = torch.Generator().manual_seed(2000 + M + nh)
-    x = (torch.randn(M, d_in, generator=g) * 20).contiguous()
-    dy = torch.randn(M, d_out, generator=g) / M
-    xd, dyd = x.to(DEV), dy.to(DEV)
-    out = torch.zeros(M, d_out, device=DEV)
-    acts = torch.zeros(nh, M, net.hp, device=DEV)
-    masks = net.mask_buffer(M)
-    forward([net], xd, d_in, 0, [out], d_out, 0, M, acts=[acts], masks=[masks])
-    L = lib()
-    s = stream_handle()
-    nblk = L.nav_mlp_row_blocks(M)
-    eslab = torch.zeros((nblk, L.nav_mlp_edge_count(d_in, d_out, net.hp, nh)), device=DEV)
-    dz = torch.zeros(nh, M, net.hp, device=DEV)
-    dx = torch.zeros(M, d_in, device=DEV)
-    L.nav_mlp_backward(descs(net), 1, M, parr(dyd), d_out, parr(masks), ptr(xd), d_in, 0,
-                       parr(acts[nh - 1]), parr(dz), (1 << nh) - 1, parr(dx), parr(eslab), s)
-    splits = 5
-    hs = torch.zeros((splits, max(4, L.nav_mlp_hidden_count(net.hp, nh))), device=DEV)
-    grad = torch.zeros(net.count, device=DEV)
-    L.nav_mlp_wgrad(descs(net), 1, M, ptr(xd), d_in, 0, parr(acts), parr(dz), parr(dyd), d_out,
-                    parr(masks), parr(hs), splits, s)
-    L.nav_grad_reduce(C.byref(net.desc()), ptr(hs), splits, ptr(eslab), nblk, ptr(grad), s)
-    torch.cuda.synchronize()
-
-    def per_row(a, ref):
-        return (a.double() - ref).abs().reshape(M, -1).amax(1), float(ref.abs().max())
-
-    rows, dW = {}, {}
-    ref, zs = _f64_forward(layers, x)
-    rows["out"] = per_row(out.cpu(), ref)
-    for l in range(nh):
-        rows[f"h{l}"] = per_row(acts[l].cpu()[:, :hidden], torch.relu(zs[l]))
-    # fp64 row backward with the kernel's ReLU bits
-    bits = relu_bits(masks, nh, net.hp, hidden, M)
-    hs64 = [x.double()] + [torch.relu(z) for z in zs]
-    for l in range(nh):
-        W, b = layers[l]
-        band = W.shape[1] * 1.2e-7 * (hs64[l].abs() @ W.double().abs().t() + b.double().abs())
-        outside = zs[l].abs() > band
-        assert torch.equal(bits[l][outside], (zs[l] > 0)[outside]), l
-    gz = dy.double() @ layers[nh][0].double()                   # dL/dh_{nh-1}
-    gW = {}
-    for l in range(nh - 1, -1, -1):
-        gz = gz * bits[l].double()                              # dL/dz_l
-        rows[f"dz{l}"] = per_row(dz[l].cpu()[:, :hidden], gz)
-        gW[l] = gz.t() @ hs64[l]
-        gz = gz @ layers[l][0].double()                         # dL/dh_{l-1} (l = 0: dL/dx)
-    rows["dx"] = per_row(dx.cpu(), gz)
-    from nav.mlp import layer_offsets
-    offs, _ = layer_offsets(d_in, d_out, net.hp, nh)
-    gflat = grad.cpu()
-    for l in range(1, nh):
-        w_off, _, fo, fi = offs[l]
-        got = gflat[w_off:w_off + fo * fi].view(fo, fi)[:hidden, :hidden]
-        dW[f"dW{l}"] = float((got.double() - gW[l]).abs().max() / gW[l].abs().max())
-    return rows, dW
 
 
 @pytest.mark.parametrize("d_in,d_out,hidden,nh", [(2, 2, 200, 3), (4, 1, 200, 3), (2, 2, 256, 2),
@@ -932,58 +809,8 @@ def test_weight_grads_tiny_inputs_stay_finite(nav, d_in, d_out):
     assert (got[:hidden, :hidden] - ref).abs().max().item() <= 1e-5 * scale
 
 
-def _fp16_image(packed, off, hp):
-    """One fp16 B image (split_entry layout [2][hp/16][2][hp][8], then int32 exponents [hp]) as
-    its two planes in fp32 [2][K][N] and the per-column exponents."""
-    n = hp * hp
-    raw = packed[off:off + n].contiguous().view(torch.float16).float()
-    P = raw.view(2, hp // 16, 2, hp, 8).permute(0, 1, 2, 4, 3).reshape(2, hp, hp)
-    e = packed[off + n:off + n + hp].contiguous().view(torch.int32)
-    return P, e
-
-
-def _pow2_exp(m):
-    """mlp_common.h pow2_exp: e with m 2^e in [2^13, 2^14), clamped to +-126; 0 for 0 / inf."""
-    import math
-    if not (m > 0) or not math.isfinite(m) or m >= 3.0e38:
-        return 0
-    _, E = math.frexp(m)
-    return max(-126, min(126, 14 - E))
-
-
-def _assert_images_exact(net, tag):
-    """Every hidden x hidden weight: the forward image (B[k][n] = W[n][k]) and the backward image
-    (B[k][n] = W[k][n]; for d_out = 1 the top layer's is Wt[k][n] = Wo[k] W[k][n] in f32) hold, per column n with e_n = pow2_exp(max_k |B[k][n]|), hi =
-    fp16_rne(B 2^e_n) and lo = fp16_rne(B 2^e_n - hi) bit for bit, and (hi + lo) 2^-e_n equals B
-    within 2^-22 of the column's max (11 + 11 significant bits)."""
-    hp, nh = net.hp, net.n_hidden
-    pk = net.packed.detach().cpu()
-    flat = net.params.detach().cpu()
-    img = hp * hp + hp
-    for L in range(1, nh):
-        w_off = net.offsets[L][0]
-        W = flat[w_off:w_off + hp * hp].view(hp, hp)
-        Wb = W
-        if net.d_out == 1 and L == nh - 1:  # the top layer's Wt image: Wo[k] * W[k][n] (f32)
-            wo = flat[net.offsets[nh][0]:net.offsets[nh][0] + hp]
-            Wb = wo[:, None] * W
-        for which, off, Bk in (("fwd", (L - 1) * 2 * img, W.t()), ("bwd", (L - 1) * 2 * img + img, Wb)):
-            P, e = _fp16_image(pk, off, hp)
-            cmax = Bk.abs().max(0).values
-            want = torch.tensor([_pow2_exp(float(m)) for m in cmax], dtype=torch.int32)
-            assert torch.equal(e, want), (tag, L, which)
-            sc = torch.pow(2.0, want.double())
-            x = (Bk.double() * sc).float()  # exact: a power of two
-            hi = x.half().float()
-            assert torch.equal(P[0], hi), (tag, L, which)
-            lo = (x - hi).half().float()
-            assert torch.equal(P[1], lo), (tag, L, which)
-            rec = (P[0].double() + P[1].double()) / sc
-            tol = 2.0 ** -22 * cmax.double() + 1e-45
-            assert ((rec - Bk.double()).abs() <= tol).all(), (tag, L, which)
-
-
-@pytest.mark.parametrize("hidden,nh", [(256, 2), (200, 3), (96, 4)])
+@pytest.mark.parametrize("hidden,nh", [(256, 2), (200, 3), (96, 4), (24, 2), (128, 3), (150, 2),
+                                       (192, 2), (40, 8)])
 def test_packed_images_exact_after_pack_adam_polyak(nav, hidden, nh):
     """The fp16 B-operand images that the hidden GEMMs read follow the weights after every writer
     (the exact two-plane decomposition of _assert_images_exact): nav_mlp_pack, nav_adam,

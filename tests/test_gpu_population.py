@@ -151,7 +151,7 @@ def tick_case(hidden, demos):
 
 
 @pytest.mark.parametrize("demos", [True, False], ids=["demos", "nodemos"])
-@pytest.mark.parametrize("hidden", [64, 256])
+@pytest.mark.parametrize("hidden", [64, 256, 24, 150])
 def test_tick_distinct_members(nav, hidden, demos):
     """P = 3 x 128 envs, members differing in actor weights, demo_factor, noise_decay,
     stuck_penalty, goal_reward and path_increase, 40 ticks from a common start, rings of 3 x 128
@@ -270,7 +270,7 @@ def rollout_case(hidden, epm):
 
 # 128: 32-row workgroups (n <= 16384); 5504 = 86 * 64: n = 16512, the 64-row side of the switch
 @pytest.mark.parametrize("epm", [EPM, 5504])
-@pytest.mark.parametrize("hidden", [64, 256])
+@pytest.mark.parametrize("hidden", [64, 256, 24, 150])
 def test_test_rollout(nav, hidden, epm):
     """Per-member actor, goal_threshold and max_action, given and drawn starts, traj, 12 steps:
     member m's slice of every output equals nav_test_rollout with actor m and params m."""

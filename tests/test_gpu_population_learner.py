@@ -139,7 +139,9 @@ def check_case(got, want):
 CASES = [(64, 2, 100),     # partial last row block, the reference's batch, split twins
          (256, 2, 2112),   # unsplit twins, the 256 x 32 factored weight-gradient tiles
          (200, 3, 100),    # hp 224, saved middle layers, k_wgrad_gen
-         (32, 1, 100)]     # no hidden x hidden weights, no pack
+         (32, 1, 100),     # no hidden x hidden weights, no pack
+         # the mlp_lpop objects of NT = hidden_pad / 32 = 3 .. 6
+         (90, 2, 100), (128, 2, 100), (150, 3, 100), (192, 2, 100)]
 
 
 @pytest.mark.parametrize("hidden,nh,B", CASES, ids=[f"h{h}x{n}_b{b}" for h, n, b in CASES])

@@ -234,7 +234,7 @@ def test_td3_update_on_philox_path_vs_oracle(nav, orc):
     3e-8 (measured on MI355X; the figure is printed).
     Measured on MI355X: max |diff| vs the oracle actor 7.5e-9, critic 1 1.5e-8, critic 2 3.0e-8,
     targets <= 1.2e-10; (i) bit-identical to (u); losses equal to 5e-8 relative."""
-    from test_gpu_mlp import relu_bits
+    from mlp_ref import relu_bits
     from test_gpu_shared_policy import make_learner, replay_rows
     from nav.vec_env import ReplayRing
     from oracle.td3_oracle import TD3Oracle, make_mlp_params

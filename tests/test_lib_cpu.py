@@ -109,3 +109,22 @@ def test_host_argument_validation(navlib):
     assert navlib.nav_mlp_hidden_count(256, 2) == 256 * 256
     empty = NavEnvSoa(0, None, None, None, None, None, None, None, None, None)
     navlib.nav_env_reset(C.byref(p), C.byref(empty), None, None, None)  # n = 0: no-op
+
+
+@pytest.mark.parametrize("hidden,hidden_pad,n_hidden", [
+    (64, 64, 9),                                     # kMaxLayers = 9: the deepest net has 8
+    (32, 0, 2), (48, 48, 2), (256, 288, 2),          # a multiple of 32 in 32 .. 256
+    (65, 64, 2)])                                    # logical width within the padded one
+def test_mlp_shape_is_validated_on_the_host(navlib, hidden, hidden_pad, n_hidden):
+    """nav_mlp_pack and nav_mlp_forward refuse a network shape that no kernel object serves
+    before any HIP call (the pointers are never followed)."""
+    from nav._lib import NavError, NavMlp
+    for d_in, d_out in ((2, 2), (4, 1)):
+        d = NavMlp(d_in, d_out, hidden, hidden_pad, n_hidden, 16, 16)
+        with pytest.raises(NavError, match="invalid argument"):
+            navlib.nav_mlp_pack(C.byref(d), None)
+        with pytest.raises(NavError, match="invalid argument"):
+            navlib.nav_mlp_forward(C.byref(d), 1, 64, 16, d_in, 0, (C.c_void_p * 1)(16), d_out,
+                                   0, 0, None, 0.2, 0.5, 5.0, 0, 0, 0, None, 0, None, None)
+        # the raw status is NAV_EINVAL, not a HIP error
+        assert navlib.raw.nav_mlp_pack(C.byref(d), None) == -100000

@@ -1,10 +1,10 @@
-"""CPU check of the test helper that decodes the kernels' ReLU bit image (tests/test_gpu_mlp.py
+"""CPU check of the test helper that decodes the kernels' ReLU bit image (tests/mlp_ref.py
 relu_bits): encode a random boolean [layers][rows][cols] pattern with the kernels' C-layout rule
 (mlp_common.h mask_idx: bit i of lane (l32, h) of row tile rt, column tile t = row
 rt*32 + (i & 3) + 8 (i >> 2) + 4 h, column t*32 + l32) and decode it back."""
 import torch
 
-from test_gpu_mlp import relu_bits
+from mlp_ref import relu_bits
 
 
 def _encode(B, hp):

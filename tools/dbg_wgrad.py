@@ -11,7 +11,7 @@ sys.path.insert(0, os.path.join(HERE, "..", "tests"))
 
 import torch  # noqa: E402
 
-from test_gpu_mlp import _f64_forward, make_net, relu_bits  # noqa: E402
+from mlp_ref import _f64_forward, make_net, relu_bits  # noqa: E402
 
 
 def run(d_in, d_out, hidden, M, splits):

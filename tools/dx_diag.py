@@ -14,7 +14,7 @@ import torch  # noqa: E402
 
 def main():
     d_in, d_out, hidden, nh, M = map(int, sys.argv[1:6])
-    from test_gpu_mlp import make_net, torch_mlp
+    from mlp_ref import make_net, torch_mlp
     from nav._lib import descs, lib, parr, ptr, stream_handle
     from nav.mlp import forward
     DEV = "cuda"
