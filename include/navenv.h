@@ -371,6 +371,23 @@ int nav_test_rollout_pop(const nav_params* params, const nav_mlp* actors, int32_
                          int32_t envs_per_member, const void* table, const nav_env_soa* env,
                          const float* field, const double* start, uint32_t episode,
                          int32_t max_steps, const nav_test_out* out, void* stream);
+/* Per-member scores of a population test rollout (device, [n_members]): what a population-based
+ * training step ranks the members by. */
+typedef struct nav_pop_score {
+    int64_t reached;        /* envs of the member with reached != 0            */
+    int64_t steps_reached;  /* sum of steps over those envs                    */
+    double  sum_best;       /* sum of best_distance over the member's envs     */
+    double  max_best;       /* max of best_distance over the member's envs     */
+} nav_pop_score;
+/* Reduces out->reached, steps and best_distance [n_members * envs_per_member], as
+ * nav_test_rollout_pop wrote them, to scores [n_members] in one launch: one workgroup per member,
+ * a strided per-thread partial, then a fixed tree; no floating-point atomics. The order of a
+ * member's sum depends on envs_per_member alone: two calls on the same input give the same bits,
+ * member m's score does not depend on n_members, the integer fields are exact. Host checks
+ * (NAV_EINVAL): n_members in 1 .. 256, envs_per_member >= 1 and a multiple of 64, none of the
+ * three inputs or `scores` null. */
+int nav_pop_test_summary(const nav_test_out* out, int32_t n_members, int32_t envs_per_member,
+                         nav_pop_score* scores, void* stream);
 
 /* Generic forward of up to 2 networks sharing one input (twin critics), rows [M]:
  * x = in[m*ld_in + in_col + 0..d_in) (f32). out_mode 0: out[m*ld_out + out_col + j] = y;
@@ -620,6 +637,34 @@ int nav_grad_reduce_adam_pop(const nav_td3_member* members, int32_t n_members, i
                              const void* table, int32_t group, float beta1, float beta2,
                              float eps, double bc1, float bc2_sqrt, int32_t soft_update,
                              void* stream);
+
+/* ---- Population-based training: clone learners inside a population in ONE launch ----
+ * For every pair j, member dst[j] receives a byte-for-byte copy of member src[j]'s learner state:
+ * `params` of the six networks (actor, critics[2], target_actor, target_critics[2]), their
+ * `packed` images (nav_mlp_packed_count floats; none for n_hidden == 1, where `packed` is not
+ * looked at), the six Adam moment buffers (m_actor, v_actor, m_critic[2], v_critic[2]) and, if
+ * replay_rows > 0, rows [0, replay_rows) of the replay ring (later rows untouched; 0 leaves dst's
+ * ring alone). Every other field of nav_td3_member (workspace, seeds, learning rates,
+ * hyper-parameters, injected indices) is neither read nor written and may be null.
+ * `state_table` is device memory of nav_td3_pop_state_bytes(n_members) bytes (n_members times
+ * the size for one, a multiple of 8) that nav_td3_pop_state_build fills on the stream with each
+ * member's segment pointers and sizes, from the same array the learner table takes: once per
+ * population, and again only when a buffer is replaced. It does not depend on the batch size or
+ * the split counts. The pair list travels by value with the launch; the launch allocates, copies
+ * and synchronises nothing (graph-capturable): grid (chunk blocks, pairs), a block walks its
+ * pair's segments as one range of 16-byte units (every segment is a whole number of them:
+ * parameter segments are rounded to 4 floats, hidden_pad is a multiple of 32, ring rows are 32
+ * bytes). Host checks (NAV_EINVAL, before any HIP call): n_members in 1 .. 256; n_pairs in
+ * 1 .. n_members - 1; every index in [0, n_members); src[j] != dst[j]; no member twice in dst;
+ * no member of dst in src (so a launch never reads what it writes; one src may serve several
+ * dst); one network shape across members and equal ring capacities; 0 <= replay_rows <=
+ * capacity; no null or non-16-byte-aligned segment pointer; state_table not null. */
+int64_t nav_td3_pop_state_bytes(int32_t n_members);
+int nav_td3_pop_state_build(const nav_td3_member* members, int32_t n_members, void* state_table,
+                            void* stream);
+int nav_td3_pop_exploit(const nav_td3_member* members, int32_t n_members,
+                        const void* state_table, const int32_t* src, const int32_t* dst,
+                        int32_t n_pairs, int64_t replay_rows, void* stream);
 
 /* ---- kernel timing (measurement only, not on the reference's interface) ----
  * Timing events recorded with a device-scope release (hipEventReleaseToDevice): bracketing a

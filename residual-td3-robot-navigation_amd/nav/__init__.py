@@ -5,11 +5,13 @@ libnavenv.so (C-ABI: include/navenv.h), with the reference's Python API on top.
     from nav import Environment, Robot          # drop-ins for environment.py / robot.py
     from nav import VecEnv, VecTrainer, TD3     # the vectorised GPU path
     from nav import PopulationTrainer, sweep_grid   # P configurations on one env set
+    from nav import pbt_select                      # population-based training's selection
 """
 from . import config  # noqa: F401
 
 __all__ = ["Environment", "Robot", "VecEnv", "VecTrainer", "TD3", "DeviceMLP", "ReplayRing",
-           "PopulationTrainer", "PopulationTable", "PopulationLearner", "sweep_grid"]
+           "PopulationTrainer", "PopulationTable", "PopulationLearner", "sweep_grid",
+           "pbt_select"]
 
 
 def __getattr__(name):
@@ -20,7 +22,8 @@ def __getattr__(name):
     if name == "VecTrainer":
         from .trainer import VecTrainer
         return VecTrainer
-    if name in ("PopulationTrainer", "PopulationTable", "PopulationLearner", "sweep_grid"):
+    if name in ("PopulationTrainer", "PopulationTable", "PopulationLearner", "sweep_grid",
+                "pbt_select"):
         from . import population
         return getattr(population, name)
     if name == "TD3":

@@ -58,6 +58,12 @@ class NavTestOut(C.Structure):
                 ("traj", _vp)]
 
 
+class NavPopScore(C.Structure):
+    """nav_pop_score: one member's reduction of a population test rollout."""
+    _fields_ = [("reached", C.c_int64), ("steps_reached", C.c_int64), ("sum_best", C.c_double),
+                ("max_best", C.c_double)]
+
+
 class NavTd3Member(C.Structure):
     """nav_td3_member: one member of the population learner (its networks, ring, moments,
     hyper-parameters, injected samples and workspace)."""
@@ -141,6 +147,7 @@ SIGNATURES = [
     ("nav_test_rollout_pop", C.c_int, [_P(NavParams), _P(NavMlp), C.c_int32, C.c_int32, _vp,
                                        _P(NavEnvSoa), _vp, _vp, C.c_uint32, C.c_int32,
                                        _P(NavTestOut), _vp]),
+    ("nav_pop_test_summary", C.c_int, [_P(NavTestOut), C.c_int32, C.c_int32, _vp, _vp]),
     ("nav_mlp_forward", C.c_int, [_P(NavMlp), C.c_int32, C.c_int64, _vp, C.c_int32, C.c_int32,
                                   _P(_vp), C.c_int32, C.c_int32, C.c_int32, _vp, C.c_float,
                                   C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -211,6 +218,10 @@ SIGNATURES = [
     ("nav_grad_reduce_adam_pop", C.c_int, [_P(NavTd3Member), C.c_int32, C.c_int64, _vp,
                                            C.c_int32, C.c_float, C.c_float, C.c_float,
                                            C.c_double, C.c_float, C.c_int32, _vp]),
+    ("nav_td3_pop_state_bytes", C.c_int64, [C.c_int32]),
+    ("nav_td3_pop_state_build", C.c_int, [_P(NavTd3Member), C.c_int32, _vp, _vp]),
+    ("nav_td3_pop_exploit", C.c_int, [_P(NavTd3Member), C.c_int32, _vp, _P(C.c_int32),
+                                      _P(C.c_int32), C.c_int32, C.c_int64, _vp]),
     ("nav_event_create", C.c_int, [_P(_vp)]),
     ("nav_event_destroy", C.c_int, [_vp]),
     ("nav_event_record", C.c_int, [_vp, _vp]),
@@ -221,7 +232,8 @@ SIGNATURES = [
 _COUNT_FNS = {"nav_mlp_param_count", "nav_mlp_packed_count", "nav_mlp_mask_count",
               "nav_mlp_row_blocks", "nav_mlp_edge_count", "nav_mlp_hidden_count",
               "nav_mlp_wgrad_splits", "nav_demo_index_res", "nav_pop_table_bytes",
-              "nav_td3_pop_table_bytes", "nav_mlp_wgrad_splits_pop"}
+              "nav_td3_pop_table_bytes", "nav_mlp_wgrad_splits_pop",
+              "nav_td3_pop_state_bytes"}
 
 
 class NavError(RuntimeError):

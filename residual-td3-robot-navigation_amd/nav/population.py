@@ -17,6 +17,13 @@ table built once, the replay fill, the Philox counter and Adam's bias correction
 m ends bit for bit as its own td3_update with the same weight-gradient split counts; those are
 chosen to fill the chip with all members' tiles, so for P > 1 they differ from a lone learner's
 (wgrad_splits= sets up a "members" run to match).
+
+Population-based training turns the grid into a search: scores() reduces every member's test
+episodes to one score struct in one launch (nav_pop_test_summary), pbt_select ranks the members
+and pairs the worst with the best, exploit() makes each of the worst a byte copy of its source's
+learner in one launch (nav_td3_pop_exploit: networks, packed images, Adam moments, ring rows),
+hands it the source's hyper-parameters and perturbs those named by `explore`; pbt_step() is the
+three in a row. Nothing of it runs unless called.
 """
 import ctypes as C
 import dataclasses
@@ -26,8 +33,8 @@ import math
 import torch
 
 from . import config as K
-from ._lib import (NavMlp, NavParams, NavReplay, NavTd3Member, lib, params_struct, ptr,
-                   stream_handle)
+from ._lib import (NavMlp, NavParams, NavPopScore, NavReplay, NavTd3Member, NavTestOut, lib,
+                   params_struct, ptr, stream_handle)
 from .cem import cem_group_demo_sets
 from .fields import make_field_device
 from .td3 import TD3
@@ -41,6 +48,57 @@ TD3_KEYS = frozenset(f.name for f in dataclasses.fields(K.TD3Config)) - {"batch_
 # neither struct: the member's starting exploration scale (robot.py:35 INITIAL_NOISE) and the
 # seed of its learner (initial weights, replay sampling, target smoothing)
 EXTRA_KEYS = frozenset({"initial_noise", "seed"})
+# population-based training. What a clone keeps of its own: its start values and its learner's
+# seed; every other override it takes from its source
+PBT_OWN_KEYS = frozenset({"initial_noise", "path_length0", "seed"})
+# the float-valued per-member fields `explore` may perturb (what the population must share stays
+# out: seeds, world_size, init_region_size, max_goal_draws, policy_update_delay, the batch size,
+# the epoch count, the network shape)
+PBT_PARAM_KEYS = frozenset({"demo_factor", "noise_decay", "stuck_penalty", "stuck_threshold",
+                            "goal_reward", "goal_threshold", "max_action"})
+PBT_TD3_KEYS = frozenset({"actor_lr", "critic_lr", "gamma", "tau", "policy_noise", "noise_clip",
+                          "max_action"})
+PBT_EXPLORE_KEYS = PBT_PARAM_KEYS | PBT_TD3_KEYS
+PBT_FACTORS = (0.8, 1.25)
+
+
+def default_fitness(score):
+    """Higher is better: the success rate, then the smaller mean best distance."""
+    return (score["success_rate"], -score["mean_best_distance"])
+
+
+def pbt_select(scores, frac=0.25, rng=None, fitness=None):
+    """The (src, dst) lists of one exploit from the members' score dicts (scores()/evaluate()
+    rows). Members are ranked best first by `fitness` (a score dict -> a sortable key, higher
+    better; default (success_rate, -mean_best_distance)), ties to the lower member index. The
+    k = floor(frac * P) worst (at least 1 for P >= 2, at most P // 2) are dst, worst first; the
+    j-th worst takes the j-th best as src, or with `rng` (a numpy.random.Generator) the
+    rng.integers(k)-th best. The two sets are disjoint, so the lists satisfy
+    nav_td3_pop_exploit's rules. P = 1 gives no pairs."""
+    P = len(scores)
+    if P < 2:
+        return [], []
+    fit = fitness or default_fitness
+    # a stable sort, reversed: equal keys keep the lower index first
+    order = sorted(range(P), key=lambda m: fit(scores[m]), reverse=True)
+    k = max(1, min(int(math.floor(frac * P)), P // 2))
+    dst = order[::-1][:k]
+    src = [order[j if rng is None else int(rng.integers(k))] for j in range(k)]
+    return src, dst
+
+
+def pbt_explore(values, explore, rng):
+    """The explore rule on a clone's inherited values: for each name of `explore` (name ->
+    (lo, hi)) the new value clip(values[name] * rng.choice([0.8, 1.25]), lo, hi). Returns the
+    dict of new values; a name that is not an explorable per-member field raises KeyError."""
+    out = {}
+    for name, (lo, hi) in (explore or {}).items():
+        if name not in PBT_EXPLORE_KEYS:
+            raise KeyError(f"{name!r} cannot be explored: not one of the float-valued per-member "
+                           f"fields {sorted(PBT_EXPLORE_KEYS)}")
+        v = float(values[name]) * float(rng.choice(PBT_FACTORS))
+        out[name] = min(max(v, float(lo)), float(hi))
+    return out
 
 
 def sweep_grid(**axes):
@@ -319,6 +377,13 @@ class PopulationTrainer:
         self.streams = int(streams)
         self._side = None
         self.learner = PopulationLearner(self.td3, self.rings) if learner == "batched" else None
+        # population-based training: the exploit events, the learner-state table
+        # (nav_td3_pop_state_build, on first use), the scores' device buffer and the generator of
+        # pbt_step's draws (seeded once from `seed`)
+        self.pbt_history = []
+        self._state = None
+        self._score_buf = None
+        self._pbt_rng = None
 
     def member_slice(self, m):
         return slice(m * self.epm, (m + 1) * self.epm)
@@ -391,6 +456,156 @@ class PopulationTrainer:
             d.update(self.members[m])
             res.append(d)
         return res
+
+    # ---- population-based training
+    def scores(self, max_steps=K.TEST_TIMEOUT * K.UPDATE_RATE, episode=0, start=None,
+               stream=None):
+        """evaluate()'s rows from one rollout launch, one reduction launch
+        (nav_pop_test_summary: fixed-order sums per member) and one device-to-host copy of the
+        [P] score structs, instead of four or five synchronising reductions per member. The
+        sums run in another order than torch's, so mean_best_distance may differ from
+        evaluate()'s in the last bits; the counts and the maximum are equal."""
+        out = self.env.test_rollout_pop(self.pop, max_steps, episode=episode, start=start,
+                                        stream=stream)
+        if self._score_buf is None:
+            self._score_buf = torch.zeros(self.P * C.sizeof(NavPopScore), dtype=torch.uint8,
+                                          device=self.device)
+        o = NavTestOut(ptr(out["reached"]), ptr(out["steps"]), ptr(out["best_distance"]), None,
+                       None)
+        lib().nav_pop_test_summary(C.byref(o), self.P, self.epm, ptr(self._score_buf),
+                                   stream_handle(stream))
+        if stream is not None:
+            stream.synchronize()
+        host = (NavPopScore * self.P).from_buffer_copy(self._score_buf.cpu().numpy().tobytes())
+        res = []
+        for m, s in enumerate(host):
+            d = {"n": self.epm,
+                 "reached": int(s.reached),
+                 "success_rate": s.reached / self.epm,
+                 "mean_steps_reached": (s.steps_reached / s.reached if s.reached
+                                        else float("nan")),
+                 "mean_best_distance": s.sum_best / self.epm,
+                 "max_best_distance": s.max_best,
+                 "max_steps": int(max_steps),
+                 "episode": int(episode)}
+            d.update(self.members[m])
+            res.append(d)
+        return res
+
+    def _state_member(self, m):
+        """Member m's learner state as a nav_td3_member: the six networks, the moments and the
+        ring; everything else stays null (nav_td3_pop_exploit neither reads nor writes it)."""
+        t, e = self.td3[m], NavTd3Member()
+        e.actor, e.target_actor = t.actor_network.desc(), t.target_actor.desc()
+        e.critics[0], e.critics[1] = t.critic_network_1.desc(), t.critic_network_2.desc()
+        e.target_critics[0] = t.target_critic_network_1.desc()
+        e.target_critics[1] = t.target_critic_network_2.desc()
+        e.replay = self.rings[m].desc()
+        oa, oc1, oc2 = t.actor_optimizer, t.critic_optimizer_1, t.critic_optimizer_2
+        e.m_actor, e.v_actor = oa.m.data_ptr(), oa.v.data_ptr()
+        e.m_critic[0], e.m_critic[1] = oc1.m.data_ptr(), oc2.m.data_ptr()
+        e.v_critic[0], e.v_critic[1] = oc1.v.data_ptr(), oc2.v.data_ptr()
+        return e
+
+    def state_table(self, stream=None, rebuild=False):
+        """(the nav_td3_member array, the device table) of the members' learner state, built on
+        first use and kept: the networks, moments and rings change in place. rebuild=True after
+        a buffer was replaced."""
+        if self._state is None or rebuild:
+            arr = (NavTd3Member * self.P)(*[self._state_member(m) for m in range(self.P)])
+            tab = torch.zeros(lib().nav_td3_pop_state_bytes(self.P), dtype=torch.uint8,
+                              device=self.device)
+            lib().nav_td3_pop_state_build(arr, self.P, ptr(tab), stream_handle(stream))
+            self._state = (arr, tab)
+        return self._state
+
+    def member_value(self, m, key):
+        """Member m's present value of a per-member field: the learner's for a TD3Config field,
+        else the nav_params field."""
+        if key in TD3_KEYS:
+            return getattr(self.td3[m].cfg, key)
+        return getattr(self.params[m], key)
+
+    def _set_member_value(self, m, key, value):
+        if key in PARAM_KEYS:
+            setattr(self.params[m], key, value)
+        if key in TD3_KEYS:
+            t = self.td3[m]
+            setattr(t.cfg, key, value)
+            if key == "actor_lr":
+                t.actor_optimizer.lr = value
+            if key == "critic_lr":
+                t.critic_optimizer_1.lr = t.critic_optimizer_2.lr = value
+
+    def exploit(self, src, dst, copy_replay=True, explore=None, rng=None, stream=None):
+        """Member dst[j] becomes a continuation of member src[j]: its six networks, their packed
+        images, the six Adam moments and (copy_replay) the filled rows of the ring are copied in
+        one launch (nav_td3_pop_exploit), then the host's books follow. dst keeps its learner's
+        seed, its envs and their state and its start values (initial_noise, path_length0); it
+        takes src's value of every other per-member field, then `explore` (name -> (lo, hi))
+        perturbs the named ones: clip(value * rng.choice([0.8, 1.25]), lo, hi). The new values go
+        to members[dst], params[dst], td3[dst].cfg and the optimizers' lr; the member table (and
+        the batched learner's) is rebuilt. Appends one event per pair to pbt_history."""
+        src, dst = [int(s) for s in src], [int(d) for d in dst]
+        if len(src) != len(dst):
+            raise ValueError("exploit: one src per dst")
+        for name in (explore or {}):  # before anything is copied
+            if name not in PBT_EXPLORE_KEYS:
+                raise KeyError(f"{name!r} cannot be explored: not one of the float-valued "
+                               f"per-member fields {sorted(PBT_EXPLORE_KEYS)}")
+        if not src:
+            return []
+        if explore and rng is None:
+            rng = self.pbt_rng()
+        arr, tab = self.state_table(stream)
+        n = len(src)
+        rows = len(self.rings[src[0]]) if copy_replay else 0
+        lib().nav_td3_pop_exploit(arr, self.P, ptr(tab), (C.c_int32 * n)(*src),
+                                  (C.c_int32 * n)(*dst), n, rows, stream_handle(stream))
+        # every per-member field but the clone's own: the members' overrides name only some
+        inherited = sorted((PARAM_KEYS | TD3_KEYS) - PBT_OWN_KEYS - {"seed_lo", "seed_hi"})
+        events = []
+        for s, d in zip(src, dst):
+            before = {k: self.member_value(d, k) for k in inherited}
+            values = {k: self.member_value(s, k) for k in inherited}
+            values.update(pbt_explore(values, explore, rng))
+            for k, v in values.items():
+                self._set_member_value(d, k, v)
+            own = {k: v for k, v in self.members[d].items() if k in PBT_OWN_KEYS}
+            taken = {k: values[k] for k in self.members[s] if k not in PBT_OWN_KEYS}
+            taken.update({k: values[k] for k in (explore or {})})
+            self.members[d] = {**own, **taken}
+            if copy_replay:
+                self.rings[d].position, self.rings[d].size = (self.rings[s].position,
+                                                              self.rings[s].size)
+            changed = {k: (before[k], values[k]) for k in inherited if before[k] != values[k]}
+            events.append({"step": self.steps, "src": s, "dst": d, "replay_rows": rows,
+                           "before": {k: b for k, (b, _) in changed.items()},
+                           "after": {k: a for k, (_, a) in changed.items()},
+                           "explored": {k: values[k] for k in (explore or {})}})
+            self.pop.params[d] = self.params[d]
+        self.pop.build(stream)
+        if self.learner is not None:
+            self.learner.rebuild(stream)
+        self.pbt_history.extend(events)
+        return events
+
+    def pbt_rng(self):
+        """The generator of pbt_step's draws, seeded once from the trainer's seed."""
+        if self._pbt_rng is None:
+            import numpy as np
+            self._pbt_rng = np.random.default_rng(self.seed)
+        return self._pbt_rng
+
+    def pbt_step(self, frac=0.25, explore=None, rng=None, copy_replay=True,
+                 max_steps=K.TEST_TIMEOUT * K.UPDATE_RATE, fitness=None, stream=None):
+        """One step of population-based training: scores(), pbt_select, exploit. Returns the
+        scores and the (src, dst) pairs. rng=None draws from pbt_rng(), so a run repeats."""
+        rng = self.pbt_rng() if rng is None else rng
+        sc = self.scores(max_steps=max_steps, stream=stream)
+        src, dst = pbt_select(sc, frac=frac, rng=rng, fitness=fitness)
+        self.exploit(src, dst, copy_replay=copy_replay, explore=explore, rng=rng, stream=stream)
+        return sc, (src, dst)
 
     def env_steps(self):
         return self.steps * self.n

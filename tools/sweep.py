@@ -8,11 +8,18 @@ numbers of evaluate().
     python tools/sweep.py --axis demo_factor=10,30,50,70 --replicas 2 --envs-per-member 4096 \\
         --train-steps 200
     python tools/sweep.py --axis initial_noise=1,0.5 --axis noise_decay=0.5,0.75,0.9 --replicas 3
+    python tools/sweep.py --reference-study --replicas 2 --pbt-every 50 \\
+        --pbt-explore demo_factor=1:100 --pbt-explore critic_lr=1e-5:1e-2
 
 --reference-study runs the four DEMO_PROXIMITY_FACTOR values of the reference's published figure
 (average_score_by_demonstration_proximity.png); the second form is simulator.py:169-200's
 INITIAL_NOISE x NOISE_DECAY x 3 runs. Replica r of a configuration differs in its learner's seed
 (seed + r): initial weights, replay sampling and target-smoothing noise.
+
+--pbt-every N turns the grid into population-based training: after every N training steps the
+members are scored on test episodes of --pbt-test-steps steps, the worst --pbt-frac of them take over
+the learners and hyper-parameters of the best (PopulationTrainer.pbt_step) and perturb the fields
+named by --pbt-explore within their bounds. One JSON line per exploit event, then the members'.
 """
 import argparse
 import json
@@ -38,6 +45,16 @@ def parse_axis(text):
         except ValueError:
             out.append(float(v))
     return name, out
+
+
+def parse_explore(text):
+    """'name=lo:hi' -> (name, (lo, hi))."""
+    name, _, bounds = text.partition("=")
+    lo, _, hi = bounds.partition(":")
+    try:
+        return name, (float(lo), float(hi))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--pbt-explore wants NAME=lo:hi: {text!r}")
 
 
 def members_of(axes, replicas, seed):
@@ -75,6 +92,16 @@ def main(argv=None):
     ap.add_argument("--test-steps", type=int, default=K.TEST_TIMEOUT * K.UPDATE_RATE)
     ap.add_argument("--seed", type=int, default=K.RANDOM_SEED)
     ap.add_argument("--no-demos", action="store_true")
+    ap.add_argument("--pbt-every", type=int, default=0, metavar="N",
+                    help="population-based training: an exploit / explore step after every N "
+                         "training steps (0 = off)")
+    ap.add_argument("--pbt-frac", type=float, default=0.25,
+                    help="the share of the members replaced per step")
+    ap.add_argument("--pbt-test-steps", type=int, default=200,
+                    help="length of the test episodes the members are scored on")
+    ap.add_argument("--pbt-explore", action="append", type=parse_explore, default=[],
+                    metavar="NAME=lo:hi", help="a per-member field the clones perturb (x 0.8 or "
+                                               "x 1.25, clipped to lo .. hi); repeatable")
     a = ap.parse_args(argv)
     axes = dict(a.axis)
     if a.reference_study:
@@ -91,8 +118,16 @@ def main(argv=None):
                            updates_per_step=a.updates_per_step, seed=a.seed,
                            envs_per_group=min(a.envs_per_group, a.envs_per_member),
                            demos=not a.no_demos, streams=a.streams, learner=a.learner)
-    for _ in range(a.train_steps):
+    if a.pbt_every < 0:
+        ap.error("--pbt-every must be at least 0")
+    explore = dict(a.pbt_explore) or None
+    for step in range(a.train_steps):
         tr.step()
+        if a.pbt_every and (step + 1) % a.pbt_every == 0 and step + 1 < a.train_steps:
+            seen = len(tr.pbt_history)
+            tr.pbt_step(frac=a.pbt_frac, explore=explore, max_steps=a.pbt_test_steps)
+            for ev in tr.pbt_history[seen:]:
+                print(json.dumps({"pbt": ev}), flush=True)
     for m, row in enumerate(tr.evaluate(max_steps=a.test_steps)):
         print(json.dumps({"member": m, "replica": replica[m], "train_steps": a.train_steps,
                           **row}), flush=True)
