@@ -40,6 +40,7 @@ extern "C" {
 #define NAV_TAG_SAMPLE 4 /* ctr = (i, 0, 4, update)           replay sample index       */
 #define NAV_TAG_TNOISE 5 /* ctr = (row, 0, 5, update)         target-smoothing noise    */
 #define NAV_TAG_TEST 6   /* ctr = (0, env, 6, episode)        test-episode start draw   */
+#define NAV_TAG_DEMO 7   /* ctr = (i, 0, 7, update)           demonstration row index   */
 
 /* Constants of constants.py / robot.py as a POD (defaults in nav_default_params). */
 typedef struct nav_params {
@@ -436,6 +437,25 @@ int nav_td3_actor_rows(const nav_mlp* actor, const nav_mlp* critic, const nav_re
                        float* acts, uint32_t save_mask, float* dz, uint32_t dz_save_mask,
                        uint16_t* masks_actor, uint16_t* masks_critic, float* edge_slabs,
                        void* stream);
+/* nav_td3_actor_rows with a behaviour-cloning term on the batch's first B_demo rows (the
+ * demonstration rows, nav_td3_mix_idx's prefix; a_b = the sampled row's own action columns):
+ *   L = -q_weight * mean_{b<B} critic(s_b, pi(s_b))
+ *       + bc_weight * (1/B_demo) * sum_{b<B_demo} sum_j (pi_j(s_b) - a_{b,j})^2
+ * The BC sum runs over the two action components and is averaged over the demonstration rows
+ * only (not mse_loss's 1/(2*B_demo)). The critic's dy seed is (float)(-q_weight/B); demonstration
+ * rows add (float)(2*bc_weight/B_demo) * (pi_j - a_j) to dL/da_j. da [B][2] holds the total dL/da;
+ * bc_part [row blocks] = each block's sum of (pi_j - a_j)^2 over its demonstration rows, added in
+ * a fixed order (0 for a block that holds none). critic == NULL is pure BC: no critic pass, q and
+ * masks_critic unused (nullable), q_weight ignored, da = the BC gradient alone. With a critic,
+ * q_weight = 1, B_demo = 0 and bc_weight = 0 every output equals nav_td3_actor_rows' bit for bit.
+ * NAV_EINVAL: B_demo < 0 or > B, bc_weight != 0 with B_demo == 0, bc_part NULL. */
+int nav_td3_actor_rows_bc(const nav_mlp* actor, const nav_mlp* critic, const nav_replay* replay,
+                          int64_t size, int64_t B, const int64_t* idx, uint32_t seed_lo,
+                          uint32_t seed_hi, uint32_t counter, int64_t B_demo, float q_weight,
+                          float bc_weight, float* batch, float* q, float* da, float* bc_part,
+                          float* acts, uint32_t save_mask, float* dz, uint32_t dz_save_mask,
+                          uint16_t* masks_actor, uint16_t* masks_critic, float* edge_slabs,
+                          void* stream);
 /* u16 words of the ReLU mask image for M rows (layout: [n_hidden][row tiles][hp/32][64]). */
 int64_t nav_mlp_mask_count(int32_t hidden_pad, int32_t n_hidden, int64_t M);
 /* Parameter gradients are produced in two parts that nav_grad_reduce combines:
@@ -548,6 +568,29 @@ int nav_mlp_pack(const nav_mlp* net, void* stream);
 int nav_replay_sample(const nav_replay* replay, int64_t size, int64_t B, const int64_t* idx,
                       uint32_t seed_lo, uint32_t seed_hi, uint32_t counter, float* batch,
                       void* stream);
+/* The sample indices of one epoch with demonstration rows mixed in (one launch, both arrays;
+ * either output may be NULL). Rows b >= B_demo get the index the row kernels draw themselves:
+ * (w.x * size) >> 32 of Philox NAV_TAG_SAMPLE at 2*counter (idx_critic) and 2*counter + 1
+ * (idx_actor). Rows b < B_demo get demo_base + ((w.x * n_demo) >> 32) of Philox NAV_TAG_DEMO,
+ * ctr = (b, 0, 7, 2*counter [+ 1]): a row of the demonstration tail behind the ring
+ * (demo_base = the ring's capacity) or of a demonstration tensor of its own (demo_base = 0).
+ * NAV_EINVAL: B < 1, size < 1, B_demo < 0 or > B, B_demo > 0 with n_demo < 1, demo_base < 0. */
+int nav_td3_mix_idx(int64_t size, int64_t B, int64_t B_demo, int64_t demo_base, int64_t n_demo,
+                    uint32_t seed_lo, uint32_t seed_hi, uint32_t counter, int64_t* idx_critic,
+                    int64_t* idx_actor, void* stream);
+/* process_demonstration's transitions (robot.py:704-716) of n_demo demonstrations of T states
+ * each as replay rows: row d*(T-1)+i = (s, a, r, s', done) with s = states[d][i],
+ * a = actions[d][i], s' = states[d][i+1], done = (i == T-2) and r = compute_reward([s']) before
+ * any demonstration is known (robot.py:741-750): gt = -||s' - goal[d]|| formed as the tick forms
+ * its goal term (in double from the f32 inputs), r = goal_reward where gt >= -goal_threshold,
+ * else gt, rounded once to f32. frame 0 (the learner's frame): the rows as above, the action raw
+ * (CEM's unclipped action, as the reference stores it). frame 1 (the acting frame): s <- s - g,
+ * s' <- s' - g, a <- clamp(a, +-max_action) - (s - g), each formed in double and rounded once:
+ * the residual the actor has to output on its input s - g for the demonstrated, clipped action.
+ * NAV_EINVAL: NULL pointers, n_demo < 1, T < 2, frame not 0 or 1. */
+int nav_demo_transitions(const nav_params* p, int32_t n_demo, int32_t T, const float* states,
+                         const float* actions, const double* goal, int32_t frame, float* rows,
+                         void* stream);
 /* Fill / strided copy helpers of the TD3 glue (robot.py:329-339, 386-390). */
 int nav_fill(float* x, int64_t n, float value, void* stream);
 int nav_strided_copy(const float* src, int32_t ld_src, int32_t col_src, float* dst, int32_t ld_dst,

@@ -1392,6 +1392,28 @@ __global__ __launch_bounds__(kBlock) void k_replay_sample(const float4* __restri
     batch[2 * b + 1] = rows[2 * k + 1];
 }
 
+// One epoch's sample indices with demonstration rows mixed in (nav_td3_mix_idx): out[0] at Philox
+// counter ctr0 (the critic's batch), out[1] at ctr0 + 1 (the actor's); rows b < B_demo from
+// NAV_TAG_DEMO over the n_demo rows at demo_base, the rest what sample_row draws itself
+struct MixIdxArgs {
+    int64_t size, B, B_demo, demo_base, n_demo;
+    uint32_t s0, s1, ctr0;
+    int64_t* out[2];
+};
+__global__ __launch_bounds__(kBlock) void k_td3_mix_idx(MixIdxArgs a) {
+    const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (b >= a.B) return;
+    const bool demo = b < a.B_demo;
+#pragma unroll
+    for (int y = 0; y < 2; ++y) {
+        if (!a.out[y]) continue;
+        const uint4 w = philox((uint32_t)b, 0u, demo ? NAV_TAG_DEMO : NAV_TAG_SAMPLE,
+                               a.ctr0 + (uint32_t)y, a.s0, a.s1);
+        a.out[y][b] = demo ? a.demo_base + (int64_t)(((uint64_t)w.x * (uint64_t)a.n_demo) >> 32)
+                           : (int64_t)(((uint64_t)w.x * (uint64_t)a.size) >> 32);
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void k_fill(float* x, int64_t n, float v) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i < n) x[i] = v;
@@ -1878,6 +1900,20 @@ int nav_replay_sample(const nav_replay* replay, int64_t size, int64_t B, const i
     hipLaunchKernelGGL(k_replay_sample, dim3(blocks_for(B)), dim3(kBlock), 0, S(stream),
                        reinterpret_cast<const float4*>(replay->rows), size, B, idx, seed_lo,
                        seed_hi, counter, reinterpret_cast<float4*>(batch));
+    NAV_CHECK_LAUNCH();
+    return 0;
+}
+
+int nav_td3_mix_idx(int64_t size, int64_t B, int64_t B_demo, int64_t demo_base, int64_t n_demo,
+                    uint32_t seed_lo, uint32_t seed_hi, uint32_t counter, int64_t* idx_critic,
+                    int64_t* idx_actor, void* stream) {
+    if (B < 1 || size < 1 || size > ((int64_t)1 << 32) || B_demo < 0 || B_demo > B ||
+        (B_demo > 0 && (n_demo < 1 || n_demo > ((int64_t)1 << 32))) || demo_base < 0)
+        return NAV_EINVAL;
+    if (!idx_critic && !idx_actor) return 0;
+    MixIdxArgs a{size, B, B_demo, demo_base, n_demo, seed_lo, seed_hi, 2u * counter,
+                 {idx_critic, idx_actor}};
+    hipLaunchKernelGGL(k_td3_mix_idx, dim3(blocks_for(B)), dim3(kBlock), 0, S(stream), a);
     NAV_CHECK_LAUNCH();
     return 0;
 }

@@ -1922,6 +1922,21 @@ struct ActorRowsArgs {
     WarmList warm;       // set by the launcher
 };
 
+// The behaviour-cloning forms of actor_rows (nav_td3_actor_rows_bc): the plain arguments (dq =
+// -q_weight/B) and, beside them, what the BC term on the batch's first B_demo rows needs. Not in
+// ActorRowsArgs: the population table stores that struct per member.
+enum { ACTOR_PLAIN = 0, ACTOR_TD3_BC = 1, ACTOR_BC_ONLY = 2 };
+struct ActorBcExtra {
+    int64_t B_demo;      // rows b < B_demo are demonstration rows
+    float bc_coef;       // 2 * bc_weight / B_demo
+    float* bc_part;      // [row blocks] block sums of (pi_j - a_j)^2 over demonstration rows
+};
+struct ActorRowsBcArgs {
+    ActorRowsArgs r;     // r.critic: the actor's descriptor again when bc_only (never read)
+    ActorBcExtra bc;
+    int bc_only;         // no critic given: the BC term alone
+};
+
 // train_actor (robot.py:382-390) for one block of TM batch rows: sample, actor forward,
 // critic-1 forward on (s, pi(s)), backward of -mean(Q) through critic 1 to its action input
 // (critic grads discarded, as zero_grad does), and the actor's row backward with its edge
@@ -1931,12 +1946,26 @@ template <int NT, int RT, int CBM>
 __global__ __launch_bounds__(kBlock, 1) void k_td3_actor_rows(ActorRowsArgs a) {
     constexpr bool POP = false;
     constexpr RowsPop pv{};
+    constexpr int MODE = ACTOR_PLAIN;
+    constexpr ActorBcExtra bx{};
 #include "td3_actor_rows_body.inc"
 }
 template <int NT, int RT, int CBM>
 __global__ __launch_bounds__(kBlock, 1) void k_td3_actor_rows_pop(RowsPop pv) {
     constexpr bool POP = true;
+    constexpr int MODE = ACTOR_PLAIN;
+    constexpr ActorBcExtra bx{};
     const ActorRowsArgs& a = static_cast<const ActorRowsArgs*>(pv.table)[blockIdx.z];
+#include "td3_actor_rows_body.inc"
+}
+// the BC forms (MODE = ACTOR_TD3_BC / ACTOR_BC_ONLY; the latter runs no critic pass, so its CBM
+// is unused and the launcher takes 1)
+template <int NT, int RT, int CBM, int MODE>
+__global__ __launch_bounds__(kBlock, 1) void k_td3_actor_rows_bc(ActorRowsBcArgs x) {
+    constexpr bool POP = false;
+    constexpr RowsPop pv{};
+    const ActorRowsArgs& a = x.r;
+    const ActorBcExtra& bx = x.bc;
 #include "td3_actor_rows_body.inc"
 }
 
@@ -1966,7 +1995,7 @@ int row_tiles_for(int64_t M, bool tick) { return (!tick && M <= kSmallRows) ? 1 
 // them through nav_mlp_rows_<NT>(). Argument structs travel as const void* (same definitions).
 enum {
     FAM_FWD = 0, FAM_BWD = 1, FAM_CRITIC = 2, FAM_ACTOR = 3, FAM_TEST = 4, FAM_TEST_POP = 5,
-    FAM_CRITIC_POP = 6, FAM_ACTOR_POP = 7
+    FAM_CRITIC_POP = 6, FAM_ACTOR_POP = 7, FAM_ACTOR_BC = 8
 };
 
 }  // namespace
@@ -1977,7 +2006,9 @@ enum {
     int nav_mlp_rows_pop_##NT_(int fam, int rt, int in_mode, int out_mode, const void* args,  \
                                int n_nets, hipStream_t st);                                   \
     int nav_mlp_rows_lpop_##NT_(int fam, int rt, int in_mode, int out_mode, const void* args, \
-                                int n_nets, hipStream_t st);
+                                int n_nets, hipStream_t st);                                  \
+    int nav_mlp_rows_bc_##NT_(int fam, int rt, int in_mode, int out_mode, const void* args,   \
+                              int n_nets, hipStream_t st);
 NAV_ROWS_DECL(1) NAV_ROWS_DECL(2) NAV_ROWS_DECL(3) NAV_ROWS_DECL(4)
 NAV_ROWS_DECL(5) NAV_ROWS_DECL(6) NAV_ROWS_DECL(7) NAV_ROWS_DECL(8)
 #undef NAV_ROWS_DECL
@@ -2052,6 +2083,30 @@ void launch_actor_rows_k(const ActorRowsArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k, dim3(gx, 1u + wy), dim3(kBlock), lds, st, w);
 }
 
+// the BC forms: actor_rows' launch with 2 * TM + 4 more LDS floats (the rows' actions and the
+// waves' BC sums, past the stage); bc_only warms the actor's images alone
+template <int NT, int RT>
+void launch_actor_rows_bc_k(const ActorRowsBcArgs& a, hipStream_t st) {
+    constexpr int TM = RT * 32;
+    const size_t lds = ((size_t)TM * (NT * 32 + 4) + TM * 4 + red_floats(TM) + TM * 8) * 4 +
+                       stage_bytes(TM, NT * 32) + (2 * TM + kBlock / 64) * 4;
+    auto k = a.bc_only                ? k_td3_actor_rows_bc<NT, RT, 1, ACTOR_BC_ONLY>
+             : a.r.critic.n_hidden == 1 ? k_td3_actor_rows_bc<NT, RT, 0, ACTOR_TD3_BC>
+                                        : k_td3_actor_rows_bc<NT, RT, 1, ACTOR_TD3_BC>;
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+    const unsigned gx = (unsigned)((a.r.B + TM - 1) / TM);
+    ActorRowsBcArgs w = a;
+    w.r.warm = WarmList{};
+    const bool ok = warm_net(w.r.warm, a.r.actor, false) &&
+                    (a.bc_only || warm_net(w.r.warm, a.r.critic, false));
+    if (!ok) w.r.warm.n = 0;
+    w.r.warm.y0 = 1;
+    const unsigned wy = warm_rows(w.r.warm, gx, 1u);
+    if (wy == 0) w.r.warm.n = 0;
+    hipLaunchKernelGGL(k, dim3(gx, 1u + wy), dim3(kBlock), lds, st, w);
+}
+
 // the population forms: grid.z = the member, no L2 warmer rows
 template <int NT, int RT>
 void launch_critic_rows_pop_k(const RowsPopLaunch& a, hipStream_t st) {
@@ -2091,7 +2146,15 @@ void launch_test_k(const TestArgs& a, hipStream_t st) {
 template <int RT>
 int rows_rt(int fam, int in_mode, int out_mode, const void* args, int n_nets, hipStream_t st) {
     constexpr int NT = NAV_MLP_PART;
-#if defined(NAV_MLP_LPOP)
+#if defined(NAV_MLP_BC)
+    // the BC forms of actor_rows, in objects of their own (mlp_bc<NT>.o) for the same reason as
+    // the population forms below
+    if (fam == FAM_ACTOR_BC) {
+        launch_actor_rows_bc_k<NT, RT>(*static_cast<const ActorRowsBcArgs*>(args), st);
+        return 0;
+    }
+    return NAV_EINVAL;
+#elif defined(NAV_MLP_LPOP)
     // the population learner's row kernels, in objects of their own too (mlp_lpop<NT>.o)
     if (fam == FAM_CRITIC_POP) {
         launch_critic_rows_pop_k<NT, RT>(*static_cast<const RowsPopLaunch*>(args), st);
@@ -2159,7 +2222,9 @@ int rows_rt(int fam, int in_mode, int out_mode, const void* args, int n_nets, hi
 
 #define NAV_CAT2(a, b) a##b
 #define NAV_CAT(a, b) NAV_CAT2(a, b)
-#if defined(NAV_MLP_LPOP)
+#if defined(NAV_MLP_BC)
+#define NAV_ROWS_NAME NAV_CAT(nav_mlp_rows_bc_, NAV_MLP_PART)
+#elif defined(NAV_MLP_LPOP)
 #define NAV_ROWS_NAME NAV_CAT(nav_mlp_rows_lpop_, NAV_MLP_PART)
 #elif defined(NAV_MLP_POP)
 #define NAV_ROWS_NAME NAV_CAT(nav_mlp_rows_pop_, NAV_MLP_PART)
@@ -2173,7 +2238,8 @@ int NAV_ROWS_NAME(int fam, int rt, int in_mode, int out_mode, const void* args, 
 }
 
 // (a trace variant builds one part with NAV_PHASE_TRACE: tools/build_variant.sh)
-#if defined(NAV_PHASE_TRACE) && !defined(NAV_MLP_POP) && !defined(NAV_MLP_LPOP)
+#if defined(NAV_PHASE_TRACE) && !defined(NAV_MLP_POP) && !defined(NAV_MLP_LPOP) && \
+    !defined(NAV_MLP_BC)
 extern "C" int nav_phase_trace_read(unsigned long long* host, int n) {
     const size_t bytes = sizeof(g_phase_trace);
     if (!host || (size_t)n * sizeof(unsigned long long) < bytes) return NAV_EINVAL;
@@ -2183,7 +2249,7 @@ extern "C" int nav_phase_trace_read(unsigned long long* host, int n) {
 #endif
 
 #if defined(NAV_CLOCK_STAMP) && NAV_MLP_PART == 8 && !defined(NAV_MLP_POP) && \
-    !defined(NAV_MLP_LPOP)
+    !defined(NAV_MLP_LPOP) && !defined(NAV_MLP_BC)
 extern "C" int nav_clock_stamp_read(unsigned long long* host, int n) {
     const size_t bytes = sizeof(g_clock_stamp);
     if (!host || (size_t)n * sizeof(unsigned long long) < bytes) return NAV_EINVAL;
@@ -2197,19 +2263,23 @@ extern "C" int nav_clock_stamp_read(unsigned long long* host, int n) {
 namespace {
 
 // hp / 32 -> the per-NT object; the population forms of the tick and the test rollout live in
-// objects of their own (row 1), and so do the population learner's row kernels (row 2)
+// objects of their own (row 1), and so do the population learner's row kernels (row 2) and the
+// BC forms of actor_rows (row 3)
 int rows_dispatch(int hp, int fam, int in_mode, int out_mode, const void* args, int n_nets,
                   int64_t M, hipStream_t st) {
-    static decltype(&nav_mlp_rows_1) const rows[3][8] = {
+    static decltype(&nav_mlp_rows_1) const rows[4][8] = {
         {nav_mlp_rows_1, nav_mlp_rows_2, nav_mlp_rows_3, nav_mlp_rows_4, nav_mlp_rows_5,
          nav_mlp_rows_6, nav_mlp_rows_7, nav_mlp_rows_8},
         {nav_mlp_rows_pop_1, nav_mlp_rows_pop_2, nav_mlp_rows_pop_3, nav_mlp_rows_pop_4,
          nav_mlp_rows_pop_5, nav_mlp_rows_pop_6, nav_mlp_rows_pop_7, nav_mlp_rows_pop_8},
         {nav_mlp_rows_lpop_1, nav_mlp_rows_lpop_2, nav_mlp_rows_lpop_3, nav_mlp_rows_lpop_4,
-         nav_mlp_rows_lpop_5, nav_mlp_rows_lpop_6, nav_mlp_rows_lpop_7, nav_mlp_rows_lpop_8}};
+         nav_mlp_rows_lpop_5, nav_mlp_rows_lpop_6, nav_mlp_rows_lpop_7, nav_mlp_rows_lpop_8},
+        {nav_mlp_rows_bc_1, nav_mlp_rows_bc_2, nav_mlp_rows_bc_3, nav_mlp_rows_bc_4,
+         nav_mlp_rows_bc_5, nav_mlp_rows_bc_6, nav_mlp_rows_bc_7, nav_mlp_rows_bc_8}};
     const int rt = row_tiles_for(
         M, fam == FAM_FWD && (out_mode == OUT_TICK || out_mode == OUT_TICK_POP));
-    const int pop = fam == FAM_CRITIC_POP || fam == FAM_ACTOR_POP ? 2
+    const int pop = fam == FAM_ACTOR_BC ? 3
+                    : fam == FAM_CRITIC_POP || fam == FAM_ACTOR_POP ? 2
                     : fam == FAM_TEST_POP || (fam == FAM_FWD && out_mode == OUT_TICK_POP) ? 1 : 0;
     if (hp < 32 || hp > 256 || (hp & 31)) return NAV_EINVAL;
     const int r = rows[pop][hp / 32 - 1](fam, rt, in_mode, out_mode, args, n_nets, st);
@@ -2694,11 +2764,44 @@ int nav_td3_actor_rows(const nav_mlp* actor, const nav_mlp* critic, const nav_re
                        uint16_t* masks_actor, uint16_t* masks_critic, float* edge_slabs,
                        void* stream) {
     ActorRowsArgs a{};
+    if (!critic) return NAV_EINVAL;
     const int rc = actor_rows_args(actor, critic, replay, size, B, idx, seed_lo, seed_hi, counter,
                                    batch, q, da, acts, save_mask, dz, dz_save_mask, masks_actor,
                                    masks_critic, edge_slabs, a);
     if (rc) return rc;
     return rows_dispatch(a.actor.hp, FAM_ACTOR, 0, 0, &a, 1, a.B, S(stream));
+}
+
+int nav_td3_actor_rows_bc(const nav_mlp* actor, const nav_mlp* critic, const nav_replay* replay,
+                          int64_t size, int64_t B, const int64_t* idx, uint32_t seed_lo,
+                          uint32_t seed_hi, uint32_t counter, int64_t B_demo, float q_weight,
+                          float bc_weight, float* batch, float* q, float* da, float* bc_part,
+                          float* acts, uint32_t save_mask, float* dz, uint32_t dz_save_mask,
+                          uint16_t* masks_actor, uint16_t* masks_critic, float* edge_slabs,
+                          void* stream) {
+    ActorRowsBcArgs x{};
+    if (B_demo < 0 || B_demo > B || (bc_weight != 0.f && B_demo == 0) || !bc_part)
+        return NAV_EINVAL;
+    // pure BC: the plain check with the actor's mask buffer standing in for the critic's
+    x.bc_only = critic ? 0 : 1;
+    const int rc = critic
+        ? actor_rows_args(actor, critic, replay, size, B, idx, seed_lo, seed_hi, counter, batch,
+                          q, da, acts, save_mask, dz, dz_save_mask, masks_actor, masks_critic,
+                          edge_slabs, x.r)
+        : actor_rows_args(actor, nullptr, replay, size, B, idx, seed_lo, seed_hi, counter, batch,
+                          nullptr, da, acts, save_mask, dz, dz_save_mask, masks_actor,
+                          masks_actor, edge_slabs, x.r);
+    if (rc) return rc;
+    if (x.bc_only) {
+        x.r.critic = x.r.actor;
+        x.r.masks_c = nullptr;
+    } else {
+        x.r.dq = (float)(-(double)q_weight / (double)B);
+    }
+    x.bc.B_demo = B_demo;
+    x.bc.bc_coef = B_demo > 0 ? (float)(2.0 * (double)bc_weight / (double)B_demo) : 0.f;
+    x.bc.bc_part = bc_part;
+    return rows_dispatch(x.r.actor.hp, FAM_ACTOR_BC, 0, 0, &x, 1, x.r.B, S(stream));
 }
 
 static int actor_rows_args(const nav_mlp* actor, const nav_mlp* critic, const nav_replay* replay,
@@ -2707,13 +2810,16 @@ static int actor_rows_args(const nav_mlp* actor, const nav_mlp* critic, const na
                            float* acts, uint32_t save_mask, float* dz, uint32_t dz_save_mask,
                            uint16_t* masks_actor, uint16_t* masks_critic, float* edge_slabs,
                            ActorRowsArgs& a) {
-    if (!actor || !critic || !replay || !replay->rows || B < 1 || size < 1 ||
+    // (critic NULL: nav_td3_actor_rows_bc's pure-BC call, no critic to check)
+    if (!actor || !replay || !replay->rows || B < 1 || size < 1 ||
         size > replay->capacity || size > ((int64_t)1 << 32) || !batch || !da ||
         (save_mask && !acts) || !masks_actor || !masks_critic || !edge_slabs ||
-        !make_dev(actor, &a.actor) || !make_dev(critic, &a.critic) || actor->d_in != 2 ||
-        actor->d_out != 2 || critic->d_in != 4 || critic->d_out != 1 ||
-        a.actor.hp != a.critic.hp || (save_mask >> actor->n_hidden) ||
-        (dz_save_mask && !dz) || (dz_save_mask >> actor->n_hidden))
+        !make_dev(actor, &a.actor) || actor->d_in != 2 || actor->d_out != 2 ||
+        (save_mask >> actor->n_hidden) || (dz_save_mask && !dz) ||
+        (dz_save_mask >> actor->n_hidden))
+        return NAV_EINVAL;
+    if (critic && (!make_dev(critic, &a.critic) || critic->d_in != 4 || critic->d_out != 1 ||
+                   a.actor.hp != a.critic.hp))
         return NAV_EINVAL;
     a.B = B;
     a.rows = replay->rows;

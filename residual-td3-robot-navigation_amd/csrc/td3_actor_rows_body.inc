@@ -1,5 +1,8 @@
 // k_td3_actor_rows' statements (mlp_kernels.hip includes this once per form, as
-// td3_critic_rows_body.inc)
+// td3_critic_rows_body.inc). MODE (constexpr, ACTOR_PLAIN in the plain and population kernels)
+// selects the behaviour-cloning forms of k_td3_actor_rows_bc, whose extras arrive in `bx`:
+// ACTOR_TD3_BC adds the BC term's gradient on rows < bx.B_demo to dL/da, ACTOR_BC_ONLY also runs
+// no critic pass. The plain forms' statements are what they were.
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if constexpr (!POP) {
         if (a.warm.n && (int)blockIdx.y >= a.warm.y0) {  // an L2 warmer row (small grids)
@@ -17,6 +20,9 @@
     float* dys = red + red_floats(TM);  // [TM][4] critic dy
     float* dys2 = dys + TM * 4;      // [TM][4] actor dy = dL/da
     _Float16* stage = reinterpret_cast<_Float16*>(dys2 + TM * 4);  // gemm_cols' split stage
+    // BC forms: the sampled rows' actions [2][TM] and the waves' BC sums, past the stage
+    [[maybe_unused]] float* bca =
+        reinterpret_cast<float*>(reinterpret_cast<char*>(stage) + stage_bytes(TM, hp));
     const L0Pre l0_a = load_l0<NT>(a.actor);  // in flight under the sampling
     NAV_CLOCK(1, 0);
     if (tid < TM) {
@@ -32,6 +38,10 @@
             dst[0] = lo;
             dst[1] = hi;
         }
+        if constexpr (MODE != ACTOR_PLAIN) {
+            bca[tid] = lo.z;
+            bca[TM + tid] = lo.w;
+        }
         *reinterpret_cast<float4*>(xin + tid * 4) = make_float4(lo.x, lo.y, 0.f, 0.f);  // s
         *reinterpret_cast<float4*>(dys + tid * 4) =
             make_float4(b < B ? a.dq : 0.f, 0.f, 0.f, 0.f);
@@ -41,12 +51,14 @@
     f32x16 topa[RT][2];
     fwd_net<NT, RT, 1, 2>(a.actor, act, stage, xin, red, a.masks_a, n_rt, a.acts, a.save_mask, row0, B, rt0,
                     topa, -64, &l0_a);
+    // (ACTOR_BC_ONLY: a.critic is the actor's descriptor again and these loads are dead)
     const L0Pre l0_c = load_l0<NT>(a.critic);  // in flight under the action epilogue
     if (tid < 2 * TM) {
         const int rloc = tid % TM, j = tid / TM;
         xin[rloc * 4 + 2 + j] = row0 + rloc < B ? out_y<RT>(a.actor, red, rloc, j) : 0.f;
     }
     __syncthreads();
+    if constexpr (MODE != ACTOR_BC_ONLY) {
     // the critic's top-layer ReLU bits and Wo columns go from its forward to its row backward in
     // registers (as in critic_rows)
     f32x16 top[RT][2];
@@ -71,6 +83,8 @@
     if (tid < TM && a.q && row0 + tid < B) a.q[row0 + tid] = out_y<RT>(a.critic, red, tid, 0);
     bwd_net<NT, RT, 1, CBM>(a.critic, act, stage, dys, xin, a.masks_c, n_rt, nullptr, nullptr,
                                     nullptr, 0u, row0, B, rt0, -64, top_bits, &wo);
+    }
+    if constexpr (MODE == ACTOR_PLAIN) {
     if (tid < 2 * TM) {
         const int rloc = tid % TM, j = tid / TM;
         const int64_t r = row0 + rloc;
@@ -78,11 +92,41 @@
         dys2[rloc * 4 + j] = v;
         if (r < B) a.da[r * 2 + j] = v;
     }
+    } else {
+        // dL/da = the critic's part (none in ACTOR_BC_ONLY) + on demonstration rows
+        // bc_coef * (pi_j - a_j); the block's sum of (pi_j - a_j)^2: the waves' sums here, added
+        // in wave order after the barrier (loss_epilogue's order)
+        float e2 = 0.f;
+        if (tid < 2 * TM) {
+            const int rloc = tid % TM, j = tid / TM;
+            const int64_t r = row0 + rloc;
+            float v = 0.f;
+            if constexpr (MODE == ACTOR_TD3_BC)
+                v = r < B ? dx_unit<NT>(a.critic, act, rloc, 2 + j) : 0.f;
+            if (r < bx.B_demo) {
+                const float d = xin[rloc * 4 + 2 + j] - bca[j * TM + rloc];
+                v += bx.bc_coef * d;
+                e2 = d * d;
+            }
+            dys2[rloc * 4 + j] = v;
+            if (r < B) a.da[r * 2 + j] = v;
+        }
+        const float w = wave_sum(e2);
+        if ((tid & 63) == 0) bca[2 * TM + (tid >> 6)] = w;
+    }
     if (tid < TM) {
         dys2[tid * 4 + 2] = 0.f;
         dys2[tid * 4 + 3] = 0.f;
     }
     __syncthreads();
+    if constexpr (MODE != ACTOR_PLAIN) {
+        if (tid == 0) {
+            float sum = 0.f;
+#pragma unroll
+            for (int k = 0; k < kBlock / 64; ++k) sum += bca[2 * TM + k];
+            bx.bc_part[blockIdx.x] = sum;
+        }
+    }
     // the actor's output layer gradient partials: dWo from its top-layer registers, dbo = column
     // sums of dL/da (bwd_net's order)
     float* es = a.eslab + (int64_t)blockIdx.x * a.ecount;

@@ -10,6 +10,7 @@ libnavenv.so (C-ABI: include/navenv.h), with the reference's Python API on top.
 from . import config  # noqa: F401
 
 __all__ = ["Environment", "Robot", "VecEnv", "VecTrainer", "TD3", "DeviceMLP", "ReplayRing",
+           "DemoReplay",
            "PopulationTrainer", "PopulationTable", "PopulationLearner", "sweep_grid",
            "pbt_select"]
 
@@ -22,6 +23,9 @@ def __getattr__(name):
     if name == "VecTrainer":
         from .trainer import VecTrainer
         return VecTrainer
+    if name == "DemoReplay":
+        from .demo_replay import DemoReplay
+        return DemoReplay
     if name in ("PopulationTrainer", "PopulationTable", "PopulationLearner", "sweep_grid",
                 "pbt_select"):
         from . import population

@@ -89,12 +89,15 @@ def device_demo_sets(states, draws, n_demos=K.NUM_DEMO, stream=None,
 
 
 def cem_group_demo_sets(field, regions, goals, seed, n_demos=K.NUM_DEMO, device="cuda",
-                        on_device=True):
+                        on_device=True, with_transitions=False):
     """Per-group demonstration sets (CSR: points [sum m_g][2] f64, offsets [G+1] int64) built the
     way the reference builds one robot's: n_demos CEM demonstrations from the group's start region
     towards its goal, each with its 3 augmentations (robot.py:679-718, 771-824). Group g draws from
     numpy RandomState((seed + g) mod 2^32). on_device: the augmentation runs as nav_demo_augment
-    and the points stay on the device; else the numpy restatement (demo_set_from) on the host."""
+    and the points stay on the device; else the numpy restatement (demo_set_from) on the host.
+    with_transitions: also the CEM's (states [G*n_demos][T][2], actions [G*n_demos][T][2]) float32
+    device tensors, group-major, and each demonstration's goal [G*n_demos][2] (numpy f64): what
+    nav.demo_replay.DemoReplay turns into replay rows."""
     G = len(regions)
     per_group = [group_stream_draws(np.random.RandomState((seed + g) & 0xFFFFFFFF), n_demos=n_demos)
                  for g in range(G)]
@@ -106,7 +109,9 @@ def cem_group_demo_sets(field, regions, goals, seed, n_demos=K.NUM_DEMO, device=
     st, ac = batched_demonstrations(field, rg, gl, uni, a0, z, device)
     draws = [[per_group[g][d][3] for d in range(n_demos)] for g in range(G)]
     if on_device:
-        return device_demo_sets(st, draws, n_demos)
+        out = device_demo_sets(st, draws, n_demos)
+        return out + (st, ac, gl) if with_transitions else out
+    st_d, ac_d = st, ac
     st, ac = st.cpu().numpy(), ac.cpu().numpy()
     pts, off = [], [0]
     for g in range(G):
@@ -114,4 +119,5 @@ def cem_group_demo_sets(field, regions, goals, seed, n_demos=K.NUM_DEMO, device=
         dset = demo_set_from(demos, draws=draws[g])
         pts.append(dset)
         off.append(off[-1] + len(dset))
-    return np.concatenate(pts, 0), np.array(off, np.int64)
+    out = (np.concatenate(pts, 0), np.array(off, np.int64))
+    return out + (st_d, ac_d, gl) if with_transitions else out

@@ -75,4 +75,10 @@ class TD3Config:
     max_action: float = ROBOT_MAX_ACTION
     batch_size: int = TD3_BATCH_SIZE
     num_epochs: int = TD3_EPOCHS
+    # learning from demonstrations (off by default): the actor's loss is -q_weight * mean Q +
+    # bc_weight * (behaviour-cloning term on the batch's demonstration rows), and demo_fraction
+    # of every batch is drawn from the demonstration tail behind the replay ring
+    bc_weight: float = 0.0
+    q_weight: float = 1.0
+    demo_fraction: float = 0.0
     net: NetConfig = field(default_factory=NetConfig)

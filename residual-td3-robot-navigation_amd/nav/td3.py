@@ -13,7 +13,7 @@ import torch
 
 from . import config as K
 from . import prof
-from ._lib import descs, lib, parr, ptr, stream_handle
+from ._lib import NavReplay, descs, lib, parr, ptr, stream_handle
 from .mlp import DeviceMLP
 
 
@@ -67,6 +67,11 @@ class TD3:
         self.critic_optimizer_2 = _Adam(self.critic_network_2, c.critic_lr)
         self.seed = seed
         self.update_counter = 0  # Philox counter for sampling / smoothing noise
+        # learning from demonstrations (cfg.demo_fraction / bc_weight / q_weight; off by default)
+        self.bc_counter = 0      # Philox counter of pretrain_bc's demonstration draws
+        self.mix_launches = 0    # nav_td3_mix_idx launches issued (0 with the feature off)
+        self._bc_ws = None       # bc_loss's workspace, by row count
+        self._last_b_demo = 0    # demonstration rows of the last BC launch (bc_loss_value)
         # shared policy (BASELINE config 5): grad_hook(bucket) SUM-all-reduces a flat gradient
         # bucket in place (nav.dist.GradAllReduce: RCCL over xGMI) and Adam divides by the hook's
         # world_size. The contract is explicit: a hook without world_size is refused, since a
@@ -116,6 +121,10 @@ class TD3:
         self.da = f(B, 2)
         self.nblk = L.nav_mlp_row_blocks(B)
         self.loss_part = f(2, self.nblk)
+        # demonstrations: the epoch's mixed sample indices and the BC term's block sums
+        self.idx_c = torch.zeros(B, dtype=torch.int64, device=d)
+        self.idx_a = torch.zeros(B, dtype=torch.int64, device=d)
+        self.bc_part = f(self.nblk)
         ec = L.nav_mlp_edge_count(4, 1, hp, nh)
         self.eslab1, self.eslab2 = f(self.nblk, ec), f(self.nblk, ec)
         self.eslab_a = f(self.nblk, L.nav_mlp_edge_count(2, 2, hp, nh))
@@ -178,7 +187,7 @@ class TD3:
         if B != self._B:
             self._workspace(B)
         key = (B, self.seed, c.policy_noise, c.noise_clip, c.max_action, c.gamma, c.tau,
-               self.split_twins)
+               self.split_twins, c.bc_weight, c.q_weight, c.demo_fraction)
         if self._st is not None and self._st_key == key:
             return self._st
         c1, c2, a = self.critic_network_1, self.critic_network_2, self.actor_network
@@ -350,7 +359,100 @@ class TD3:
         self._adam(self._static()["a"], stream_handle(stream), grad_div)
 
     def actor_loss_value(self):
-        return -(self.q1.sum() / self._B).item()
+        if not self.bc_on():
+            return -(self.q1.sum() / self._B).item()
+        return -self.cfg.q_weight * (self.q1.sum() / self._B).item() + \
+            self.cfg.bc_weight * self.bc_loss_value()
+
+    def bc_loss_value(self):
+        """The last BC launch's term: sum_j (pi_j(s) - a_j)^2 averaged over its demonstration
+        rows (0 without any), synchronising."""
+        n = self._last_b_demo
+        return (self.bc_part.double().sum() / n).item() if n else 0.0
+
+    # ---- learning from demonstrations
+    def bc_on(self):
+        return self.cfg.demo_fraction != 0 or self.cfg.bc_weight != 0
+
+    def b_demo(self):
+        """Demonstration rows per batch: the batch's first round(demo_fraction * B) rows."""
+        n = int(round(self.cfg.demo_fraction * self.cfg.batch_size))
+        if not 0 <= n <= self.cfg.batch_size:
+            raise ValueError("demo_fraction must lie in [0, 1]")
+        if self.cfg.bc_weight != 0 and n == 0:
+            raise ValueError("bc_weight needs demonstration rows in the batch: demo_fraction * "
+                             "batch_size rounds to 0")
+        return n
+
+    def _mix(self, size, b_demo, demo_base, n_demo, counter, idx_c, idx_a, s):
+        self.mix_launches += 1
+        self._run("mix_idx", 16.0 * self._B, lib().nav_td3_mix_idx, size, self._B, b_demo,
+                  demo_base, n_demo, *self._static()["seed"], counter, ptr(idx_c), ptr(idx_a), s)
+
+    def _actor_rows_bc(self, critic, replay_ref, size, idx, b_demo, q_weight, bc_weight, s):
+        """The BC form of _actor_rows into the same workspace (critic None: the BC term alone)."""
+        st = self._static()
+        self._last_b_demo = b_demo
+        t = st["ar_tail"]
+        self._run("actor_rows_bc", st["ar_work"], lib().nav_td3_actor_rows_bc, st["ar_head"][0],
+                  st["ar_head"][1] if critic else None, replay_ref, size, self._B, ptr(idx),
+                  *st["seed"], self.update_counter, b_demo, q_weight, bc_weight, t[0],
+                  t[1] if critic else None, t[2], ptr(self.bc_part), *t[3:8],
+                  t[8] if critic else None, t[9], s)
+        return st["a"]
+
+    def pretrain_bc(self, rows, epochs, batch=None, lr=None, stream=None):
+        """Pure behaviour cloning of the actor on the demonstration rows `rows` [n][8] (the
+        acting frame, DemoReplay.rows1): per epoch one nav_td3_mix_idx (every row of the batch a
+        demonstration row), the critic-free BC form of the actor row kernel, then the actor's
+        usual weight gradients, reduce and Adam step; at the end the target actor is the actor.
+        batch: rows per epoch (default cfg.batch_size); lr: the actor's Adam step size for these
+        epochs only."""
+        n = int(rows.shape[0])
+        assert rows.shape == (n, 8) and rows.is_contiguous() and n >= 1
+        c, opt = self.cfg, self.actor_optimizer
+        keep = (c.batch_size, opt.lr)
+        if batch is not None:
+            c.batch_size = int(batch)
+        if lr is not None:
+            opt.lr = float(lr)
+        s = stream_handle(stream)
+        rd = NavReplay(rows.data_ptr(), n)
+        try:
+            self._static()
+            B = self._B
+            for _ in range(int(epochs)):
+                self._mix(n, B, 0, n, self.bc_counter, None, self.idx_a, s)
+                g = self._actor_rows_bc(False, C.byref(rd), n, self.idx_a, B, 0.0, 1.0, s)
+                self._step(g, s, stream)
+                self.bc_counter += 1
+        finally:
+            c.batch_size, opt.lr = keep
+        self.target_actor.copy_from(self.actor_network)
+
+    def bc_loss(self, rows, stream=None):
+        """The BC term sum_j (pi_j(s) - a_j)^2 of the online actor averaged over all of `rows`
+        [n][8], taken in order (idx = arange): deterministic. Changes no learner state."""
+        n = int(rows.shape[0])
+        assert rows.shape == (n, 8) and rows.is_contiguous() and n >= 1
+        a, L, d = self.actor_network, lib(), self.device
+        if self._bc_ws is None or self._bc_ws["n"] != n:
+            f = lambda *sh: torch.zeros(*sh, dtype=torch.float32, device=d)  # noqa: E731
+            nblk = L.nav_mlp_row_blocks(n)
+            mid = a.middle_layers()
+            self._bc_ws = dict(
+                n=n, idx=torch.arange(n, dtype=torch.int64, device=d), batch=f(n, 8), da=f(n, 2),
+                acts=f(a.n_hidden, n, a.hp) if mid else None,
+                dz=f(a.n_hidden, n, a.hp) if mid else None, mask=a.mask_buffer(n),
+                part=f(nblk), es=f(nblk, L.nav_mlp_edge_count(2, 2, a.hp, a.n_hidden)), mid=mid)
+        w = self._bc_ws
+        rd = NavReplay(rows.data_ptr(), n)
+        ad = a.desc()
+        L.nav_td3_actor_rows_bc(C.byref(ad), None, C.byref(rd), n, n, ptr(w["idx"]), 0, 0, 0, n,
+                                0.0, 1.0, ptr(w["batch"]), None, ptr(w["da"]), ptr(w["part"]),
+                                ptr(w["acts"]), w["mid"], ptr(w["dz"]), w["mid"], ptr(w["mask"]),
+                                None, ptr(w["es"]), stream_handle(stream))
+        return (w["part"].double().sum() / n).item()
 
     # robot.py:293-310
     def soft_update(self, target, source, tau, stream=None):
@@ -385,6 +487,9 @@ class TD3:
     def _update(self, replay, n, idx_fn, eps_fn, stream, track_losses, collect_ready):
         if len(replay) < 1:
             return
+        if self.bc_on():
+            return self._update_bc(replay, n, idx_fn, eps_fn, stream, track_losses,
+                                   collect_ready)
         for epoch in range(n):
             if (collect_ready is not None and epoch == n - 1 and self.grad_hook is not None and
                     epoch % self.cfg.policy_update_delay != 0):
@@ -401,6 +506,41 @@ class TD3:
                     self.actor_losses.append(self.actor_loss_value())
             self.update_counter += 1
 
+    def _update_bc(self, replay, n, idx_fn, eps_fn, stream, track_losses, collect_ready):
+        """_update with demonstrations: per epoch one nav_td3_mix_idx (the first b_demo rows of
+        both batches from the tail behind the ring), the unchanged critic launch on idx_critic,
+        and on a policy epoch the BC form of the actor launch on idx_actor; the weight gradients,
+        reduce and Adam as ever. An explicit idx_fn still wins over the mix (its first b_demo
+        indices are then taken to address demonstration rows)."""
+        c = self.cfg
+        self._static()
+        b_demo = self.b_demo()
+        n_tail = int(replay.tail.shape[0]) if hasattr(replay, "tail") else 0
+        if b_demo and not idx_fn and n_tail < 1:
+            raise ValueError("demo_fraction > 0 needs a replay ring with a demonstration tail")
+        s = stream_handle(stream)
+        for epoch in range(n):
+            if (collect_ready is not None and epoch == n - 1 and self.grad_hook is not None and
+                    epoch % c.policy_update_delay != 0):
+                self._ready = collect_ready
+            policy = epoch % c.policy_update_delay == 0
+            if idx_fn:
+                idx_c, idx_a = idx_fn(), (idx_fn() if policy else None)
+            else:
+                idx_c, idx_a = self.idx_c, self.idx_a
+                self._mix(len(replay), b_demo, replay.capacity, n_tail, self.update_counter,
+                          idx_c, idx_a if policy else None, s)
+            self.train_critic(replay, idx=idx_c, eps=eps_fn() if eps_fn else None, stream=stream)
+            if track_losses:
+                self.critic_losses.append(sum(self.critic_loss_values()) / 2)
+            if policy:
+                g = self._actor_rows_bc(True, self._replay_ref(replay), len(replay), idx_a,
+                                        b_demo, c.q_weight, c.bc_weight, s)
+                self._step(g, s, stream, soft_update=True)
+                if track_losses:
+                    self.actor_losses.append(self.actor_loss_value())
+            self.update_counter += 1
+
     def networks(self):
         return {"actor": self.actor_network, "critic1": self.critic_network_1,
                 "critic2": self.critic_network_2, "target_actor": self.target_actor,
@@ -413,6 +553,8 @@ class TD3:
                                                      ("critic1", self.critic_optimizer_1),
                                                      ("critic2", self.critic_optimizer_2))}
         sd["update_counter"] = self.update_counter
+        if self.bc_counter:
+            sd["bc_counter"] = self.bc_counter
         return sd
 
     def load_state_dict(self, sd):
@@ -422,3 +564,4 @@ class TD3:
         self.critic_optimizer_1.load_state_dict(sd["opt"]["critic1"])
         self.critic_optimizer_2.load_state_dict(sd["opt"]["critic2"])
         self.update_counter = sd["update_counter"]
+        self.bc_counter = sd.get("bc_counter", 0)

@@ -18,6 +18,7 @@ from . import config as K
 from . import prof
 from ._lib import lib, ptr, stream_handle
 from .cem import cem_group_demo_sets
+from .demo_replay import DemoReplay
 from .fields import make_field_device
 from .td3 import TD3
 from .vec_env import ReplayRing, VecEnv
@@ -26,7 +27,12 @@ from .vec_env import ReplayRing, VecEnv
 class VecTrainer:
     def __init__(self, n_envs=65536, hidden=256, n_hidden=2, batch=32768, updates_per_step=2,
                  replay_capacity=None, seed=K.RANDOM_SEED, envs_per_group=1024, demos=True,
-                 device="cuda", field=None, grad_hook=None, fuse_tick=True, overlap_collect=False):
+                 device="cuda", field=None, grad_hook=None, fuse_tick=True, overlap_collect=False,
+                 demo_fraction=0.0, bc_weight=0.0, q_weight=1.0, demo_rows=None):
+        """demo_fraction / bc_weight / q_weight: learning from the demonstrations (TD3Config; off
+        by default). With demo_fraction or bc_weight non-zero the CEM demonstrations' transitions
+        sit in a tail behind the replay ring and a share of every batch is drawn from it (needs
+        demos=True, or demo_rows = (frame-0 rows, frame-1 rows) from a checkpoint)."""
         self.n = int(n_envs)
         self.device = torch.device(device)
         self.seed = int(seed)
@@ -43,14 +49,36 @@ class VecTrainer:
             goals = self.env.goal[firsts].cpu().numpy()
             # each group's 3 demonstrations from the batched GPU CEM (environment.py:140-179) +
             # their augmentations (robot.py:771-824), as the reference's robot acquires them
-            pts, off = cem_group_demo_sets(self.field, regions, goals, self.seed,
-                                           device=self.device)
+            pts, off, *self._cem = cem_group_demo_sets(self.field, regions, goals, self.seed,
+                                                       device=self.device, with_transitions=True)
             self.env.set_demo(pts, off if G > 1 else None)
+        else:
+            self._cem = None  # the CEM's (states, actions, goals), kept for the DemoReplay
         cfg = K.TD3Config(batch_size=int(batch), num_epochs=int(updates_per_step),
-                          net=K.NetConfig(hidden=hidden, n_hidden=n_hidden))
+                          net=K.NetConfig(hidden=hidden, n_hidden=n_hidden),
+                          bc_weight=float(bc_weight), q_weight=float(q_weight),
+                          demo_fraction=float(demo_fraction))
         self.td3 = TD3(cfg, device=self.device, seed=self.seed, grad_hook=grad_hook)
         cap = replay_capacity or max(4 * self.n, 2 * int(batch), K.BUFFER_SIZE)
-        self.replay = ReplayRing(cap, self.device)
+        # the demonstration transitions: in the ring's tail when the learner draws from them,
+        # else built on the first pretrain_bc / bc_loss (no tail: the ring is what it was)
+        self.demo_replay = None
+        if self.td3.bc_on():
+            self.td3.b_demo()  # validates demo_fraction / bc_weight against the batch size
+            if demo_rows is not None:
+                self.replay = ReplayRing(cap, self.device, tail=demo_rows[0].shape[0])
+                self.demo_replay = DemoReplay.from_rows(demo_rows[0], demo_rows[1], self.replay)
+            elif self._cem is not None:
+                st, ac, gl = self._cem
+                self.replay = ReplayRing(cap, self.device, tail=st.shape[0] * (st.shape[1] - 1))
+                self.demo_replay = DemoReplay(st, ac, gl, self.env.p, ring=self.replay)
+            else:
+                raise ValueError("demo_fraction / bc_weight need demonstrations: demos=True")
+        else:
+            self.replay = ReplayRing(cap, self.device)
+            if demo_rows is not None:
+                self.demo_replay = DemoReplay.from_rows(demo_rows[0].to(self.device),
+                                                        demo_rows[1])
         self.action = torch.zeros(self.n, 2, dtype=torch.float64, device=self.device)
         self.steps = 0
         self.updates_per_step = int(updates_per_step)
@@ -143,6 +171,25 @@ class VecTrainer:
                 "max_steps": int(max_steps),
                 "episode": int(episode)}
 
+    # ---- the imitation baseline (the reference README's "baseline policy by imitation")
+    def _demos(self):
+        if self.demo_replay is None:
+            if self._cem is None:
+                raise ValueError("no demonstrations: construct with demos=True")
+            self.demo_replay = DemoReplay(*self._cem, self.env.p)
+        return self.demo_replay
+
+    def pretrain_bc(self, epochs, batch=None, lr=None, stream=None):
+        """Pure behaviour cloning of the actor on the demonstrations in the acting frame
+        (TD3.pretrain_bc on the frame-1 rows), before any environment step: afterwards evaluate()
+        scores baseline + actor(s - g) as an imitation of the demonstrated actions."""
+        self.td3.pretrain_bc(self._demos().rows1, epochs, batch, lr, stream)
+        self.sync_collect()
+
+    def bc_loss(self, frame=1):
+        """The actor's BC loss over every demonstration row of `frame`, in order."""
+        return self.td3.bc_loss(self._demos().rows(frame))
+
     def env_steps(self):
         return self.steps * self.n
 
@@ -161,7 +208,10 @@ class VecTrainer:
                      "hidden": self.td3.actor_network.hidden,
                      "n_hidden": self.td3.actor_network.n_hidden,
                      "batch": self.td3.cfg.batch_size, "updates_per_step": self.updates_per_step,
-                     "steps": self.steps},
+                     "steps": self.steps, "demo_fraction": self.td3.cfg.demo_fraction,
+                     "bc_weight": self.td3.cfg.bc_weight, "q_weight": self.td3.cfg.q_weight},
+            "demo_rows": None if self.demo_replay is None else
+            {"rows0": self.demo_replay.rows0.cpu(), "rows1": self.demo_replay.rows1.cpu()},
             "env": {k: getattr(e, k).detach().cpu() for k in self.ENV_STATE},
             "field": self.field.detach().cpu(),
             "demo_xy": None if e.demo_xy is None else e.demo_xy.cpu(),
@@ -193,11 +243,15 @@ class VecTrainer:
         """A trainer resumed from state_dict() without re-running the field generator or the CEM
         (their results are in the checkpoint)."""
         m = sd["meta"]
+        dr = sd.get("demo_rows")
         t = cls(n_envs=m["n_envs"], hidden=m["hidden"], n_hidden=m["n_hidden"],
                 batch=m["batch"], updates_per_step=m["updates_per_step"],
                 replay_capacity=sd["replay"]["rows"].shape[0], seed=m["seed"],
                 envs_per_group=m["envs_per_group"], demos=False, device=device,
-                field=sd["field"].to(device), grad_hook=grad_hook)
+                field=sd["field"].to(device), grad_hook=grad_hook,
+                demo_fraction=m.get("demo_fraction", 0.0), bc_weight=m.get("bc_weight", 0.0),
+                q_weight=m.get("q_weight", 1.0),
+                demo_rows=None if dr is None else (dr["rows0"], dr["rows1"]))
         t.load_state_dict(sd)
         return t
 

@@ -75,13 +75,23 @@ class ReplayRing:
     """ReplayBuffer (robot.py:58-124) as a device ring of 32-byte rows
     (s0 s1 a0 a1 r s'0 s'1 done, float32)."""
 
-    def __init__(self, capacity, device="cuda", rows=None):
+    def __init__(self, capacity, device="cuda", rows=None, tail=0):
         self.capacity = int(capacity)
+        n_tail = int(tail)
         if rows is None:
-            rows = torch.zeros(self.capacity, 8, dtype=torch.float32, device=device)
-        # (rows given: a [capacity][8] slice of a population's ring tensor)
+            # `tail` demonstration rows behind the ring, in the same allocation: a sample index
+            # k >= capacity addresses tail[k - capacity] through the row kernels' `idx`; desc(),
+            # advance() and the ticks see the [capacity][8] ring alone
+            self.storage = torch.zeros(self.capacity + n_tail, 8, dtype=torch.float32,
+                                       device=device)
+            rows = self.storage[:self.capacity]
+        else:
+            # (rows given: a [capacity][8] slice of a population's ring tensor, no tail)
+            assert n_tail == 0
+            self.storage = rows
         assert rows.shape == (self.capacity, 8) and rows.is_contiguous()
         self.rows = rows
+        self.tail = self.storage[self.capacity:]
         self.position = 0  # next write slot (robot.py:77)
         self.size = 0
 

@@ -3,6 +3,11 @@ episode per env (VecTrainer.evaluate -> nav_test_rollout, one launch), printed a
 
 python tools/evaluate.py --checkpoint run.pt
 python tools/evaluate.py --n-envs 4096 --hidden 256 --n-hidden 2 --seed 7 --train-steps 200
+python tools/evaluate.py --n-envs 4096 --train-steps 0 --bc-pretrain 500 --bc-lr 1e-3
+
+--bc-pretrain N first clones the demonstrations into the actor (VecTrainer.pretrain_bc: the
+reference README's baseline policy by imitation) and adds the BC loss over all demonstration rows
+before and after to the line; --bc-weight / --demo-fraction train with the demonstrations mixed in.
 """
 import argparse
 import json
@@ -27,6 +32,10 @@ def main():
     ap.add_argument("--train-steps", type=int, default=0)
     ap.add_argument("--max-steps", type=int, default=K.TEST_TIMEOUT * K.UPDATE_RATE)
     ap.add_argument("--episode", type=int, default=0)
+    ap.add_argument("--bc-pretrain", type=int, default=0, help="BC epochs before any env step")
+    ap.add_argument("--bc-lr", type=float, default=None, help="the actor's lr while pretraining")
+    ap.add_argument("--bc-weight", type=float, default=0.0)
+    ap.add_argument("--demo-fraction", type=float, default=0.0)
     args = ap.parse_args()
     import torch
     from nav._lib import require_gpu
@@ -37,12 +46,20 @@ def main():
     else:
         tr = VecTrainer(n_envs=args.n_envs, hidden=args.hidden, n_hidden=args.n_hidden,
                         batch=args.batch or max(args.n_envs // 2, 1), seed=args.seed,
-                        envs_per_group=min(1024, args.n_envs), demos=not args.no_demos)
+                        envs_per_group=min(1024, args.n_envs), demos=not args.no_demos,
+                        bc_weight=args.bc_weight, demo_fraction=args.demo_fraction)
+    bc = {}
+    if args.bc_pretrain > 0:
+        bc["bc_loss_before"] = tr.bc_loss(frame=1)
+        tr.pretrain_bc(args.bc_pretrain, lr=args.bc_lr)
+        bc["bc_loss_after"] = tr.bc_loss(frame=1)
+        bc["bc_epochs"] = args.bc_pretrain
     for _ in range(args.train_steps):
         tr.step()
     res = tr.evaluate(max_steps=args.max_steps, episode=args.episode)
     torch.cuda.synchronize()
     res["train_steps"] = tr.steps
+    res.update(bc)
     # strict JSON: a NaN (no env reached) prints as null
     print(json.dumps({k: None if isinstance(v, float) and v != v else v for k, v in res.items()}))
 
