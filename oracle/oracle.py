@@ -352,7 +352,7 @@ def smoothing_noise(p, B, ctr):
 def learner_counters(update_counter):
     """The Philox counters TD3 epoch `update_counter` draws with (nav/td3.py passes update_counter
     to both row launches; nav_td3_critic_rows and nav_td3_actor_rows derive, in uint32,
-    mlp_kernels.hip:2535-2536, 2572): the critic's batch 2 c, the actor's batch 2 c + 1, the
+    mlp_abi.hip critic_rows_args / actor_rows_args): the critic's batch 2 c, the actor's batch 2 c + 1, the
     smoothing noise c."""
     c = int(update_counter) & 0xFFFFFFFF
     return {"critic_sample": (2 * c) & 0xFFFFFFFF, "actor_sample": (2 * c + 1) & 0xFFFFFFFF,

@@ -10,8 +10,6 @@ namespace {
 
 using namespace nav;
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 // one thread per (demonstration d, step i < T-1): row d*(T-1)+i
 __global__ __launch_bounds__(kBlock) void k_demo_transitions(
     nav_params p, int64_t n_rows, int32_t T, const float2* __restrict__ states,

@@ -995,7 +995,6 @@ __global__ __launch_bounds__(kBlock) void k_compute_reward(nav_params p, int64_t
 }
 
 inline int blocks_for(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 }  // namespace
 

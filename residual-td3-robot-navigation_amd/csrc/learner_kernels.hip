@@ -2,8 +2,9 @@
 // gfx950: hidden x hidden weight gradients on MFMA, the fixed-order gradient reduce fused with
 // torch's Adam, multi-net Adam for the shared-policy bucket, Polyak soft updates (all refreshing
 // the packed MFMA weight images), and the replay sampling / copy glue. The row-local half
-// (forward, row backward, the fused train_critic / train_actor row programs) is mlp_kernels.hip.
+// (forward, row backward, the fused train_critic / train_actor row programs) is mlp_rows.h.
 #include "mlp_common.h"
+#include "pop_host.h"
 
 namespace {
 
@@ -1067,7 +1068,7 @@ struct PackInfo {
 // hp / 16 <= 16 k chunks: one load round trip and no second pass over W.
 // For d_out = 1 the TOP hidden layer's backward image holds Wt[k][n] = Wo[k] * W_L[k][n] (f32
 // products) instead of W_L: the row backward's top GEMM then takes the forward's ReLU bits as
-// its exact fp16 A operand and applies dL/dq per row after the sum (mlp_kernels.hip gemm_bits).
+// its exact fp16 A operand and applies dL/dq per row after the sum (mlp_rows.h gemm_bits).
 struct PackJob {
     const float* p;
     PackInfo pk;
@@ -1957,8 +1958,6 @@ extern "C" int nav_wgrad_trace_read(unsigned long long* host, int n) {
 // holds what it held before.
 namespace {
 
-constexpr int kMaxMembers = 256;
-
 struct LearnMember {
     WgradArgs wg[2];   // group 0: the twin critics, group 1: the actor
     RedArgs red[3];    // the critics' step, the actor's, the actor's with the three soft updates
@@ -2047,24 +2046,12 @@ int learn_member_fill(const nav_td3_member& t, int64_t B, int32_t sc, int32_t sa
     return 0;
 }
 
-bool same_shape(const nav_mlp& a, const nav_mlp& b) {
-    return a.d_in == b.d_in && a.d_out == b.d_out && a.hidden == b.hidden &&
-           a.hidden_pad == b.hidden_pad && a.n_hidden == b.n_hidden;
-}
-
 // the check every entry point shares; e0 / blocks: member 0's entry (the launch shape)
 int learn_pop_check(const nav_td3_member* members, int32_t n_members, int64_t B, int32_t sc,
                     int32_t sa, LearnMember* dst, LearnMember& e0, int (&blocks)[3]) {
-    if (!members || n_members < 1 || n_members > kMaxMembers || B < 1) return NAV_EINVAL;
+    if (!members_same_shape(members, n_members) || B < 1) return NAV_EINVAL;
     for (int m = 0; m < n_members; ++m) {
         const nav_td3_member& t = members[m];
-        const nav_td3_member& t0 = members[0];
-        if (!same_shape(t.actor, t0.actor) || !same_shape(t.target_actor, t0.target_actor))
-            return NAV_EINVAL;
-        for (int i = 0; i < 2; ++i)
-            if (!same_shape(t.critics[i], t0.critics[i]) ||
-                !same_shape(t.target_critics[i], t0.target_critics[i]))
-                return NAV_EINVAL;
         LearnMember e{};
         int bl[3] = {0, 0, 0};
         const int rc = learn_member_fill(t, B, sc, sa, e, bl);

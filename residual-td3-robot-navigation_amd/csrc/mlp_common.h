@@ -1,5 +1,5 @@
 // mlp_common.h — the device MLP layout (include/navenv.h nav_mlp) and the fragment helpers
-// shared by the row kernels (mlp_kernels.hip) and the learner kernels (learner_kernels.hip).
+// shared by the row kernels (mlp_rows.h) and the learner kernels (learner_kernels.hip).
 #pragma once
 #include <stdlib.h>
 
@@ -8,27 +8,15 @@
 using namespace nav;
 
 // The population learner's table (nav_td3_pop_table_build) is [n_members] row-kernel arguments
-// (mlp_kernels.hip) followed by [n_members] entries of the cross-row kernels
+// (mlp_rows.h) followed by [n_members] entries of the cross-row kernels
 // (learner_kernels.hip built with NAV_LEARNER_POP): that object's size and its check + fill of
 // members' entries into host memory `dst` (NULL: check only), called by the table's entry points.
 int64_t navi_learner_pop_entry_bytes();
-int64_t navi_rows_pop_entry_bytes();  // (mlp_kernels.hip's, a multiple of 8)
+int64_t navi_rows_pop_entry_bytes();  // (mlp_abi.hip's, a multiple of 8)
 int navi_learner_pop_fill(const nav_td3_member* members, int32_t n_members, int64_t B,
                           int32_t splits_critic, int32_t splits_actor, void* dst);
 
 namespace {
-
-// `n` 32-bit words of a host-built table entry, passed by value and written by the stream's
-// kernel (stream-ordered, no host memory outlives the call; a template so that only the objects
-// that build tables hold it)
-template <int W>
-struct TableChunk {
-    uint32_t w[W];
-};
-template <int W>
-__global__ void k_table_chunk_write(TableChunk<W> c, uint32_t* dst, int n) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = c.w[i];
-}
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -93,8 +81,6 @@ __host__ __device__ inline int64_t edge_to_flat(const MlpDev& d, int64_t e) {
     const int64_t L = (e - d.w_off[1]) / d.hp + 1;  // inside the b_L run
     return e + L * d.hp * d.hp;
 }
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ReLU as an integer max of the bit pattern: one v_max_i32 (fmaxf costs a NaN-quieting
 // v_max_f32 x, x first). Negative values and -0 give +0; finite results equal fmaxf(v, 0).

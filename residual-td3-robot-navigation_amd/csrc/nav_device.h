@@ -16,6 +16,9 @@ constexpr int kBlock = 256;
 // pairs (b, b + kCUs) on one CU (profiles/r04x wide phase trace).
 constexpr int kCUs = 256;
 
+// the C ABI's stream argument
+inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
 // Philox4x32-10 (Salmon et al. 2011); key (k0,k1), counter (c0..c3).
 NAV_DEV uint4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                      uint32_t k1) {

@@ -1,18 +1,15 @@
 // pop_state.hip — population-based training on one device: the per-member scores of a population
 // test rollout (nav_pop_test_summary) and the cloning of learners inside a population
-// (nav_td3_pop_state_build, nav_td3_pop_exploit). A translation unit of its own: every other
+// (nav_td3_pop_state_build, nav_td3_pop_exploit), and the writer of every host-built population
+// table (navi_table_write, pop_host.h). A translation unit of its own: every other
 // object of libnavenv.so compiles from the source and with the flags it had before.
 #include <stdlib.h>
 
-#include "nav_device.h"
+#include "pop_host.h"
 
 namespace {
 
 using namespace nav;
-
-constexpr int kMaxMembers = 256;
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ---------------- scores ----------------
 // One workgroup per member: thread t folds envs t, t + 256, .. of the member in that order, then a
@@ -113,7 +110,7 @@ __global__ void k_pop_exploit(const StateMember* __restrict__ tab, PairList pair
     }
 }
 
-// 2 KB of kernel argument per write of the table (stream-ordered, no host memory outlives the call)
+// 2 KB of kernel argument per write of a table (navi_table_write)
 constexpr int kChunkWords = 512;
 struct StateChunk {
     uint32_t w[kChunkWords];
@@ -123,11 +120,6 @@ __global__ void k_state_chunk_write(StateChunk c, uint32_t* dst, int n) {
 }
 
 bool aligned16(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-bool same_shape(const nav_mlp& a, const nav_mlp& b) {
-    return a.d_in == b.d_in && a.d_out == b.d_out && a.hidden == b.hidden &&
-           a.hidden_pad == b.hidden_pad && a.n_hidden == b.n_hidden;
-}
 
 void member_nets(const nav_td3_member& t, const nav_mlp* (&nets)[kNets]) {
     nets[0] = &t.actor;
@@ -141,7 +133,7 @@ void member_nets(const nav_td3_member& t, const nav_mlp* (&nets)[kNets]) {
 // The host check the state entry points share (before any HIP call); dst (nullable):
 // [n_members] host entries
 int state_check(const nav_td3_member* members, int32_t n_members, StateMember* dst) {
-    if (!members || n_members < 1 || n_members > kMaxMembers) return NAV_EINVAL;
+    if (!members_same_shape(members, n_members)) return NAV_EINVAL;
     const nav_mlp* nets0[kNets];
     member_nets(members[0], nets0);
     int64_t params16[kNets], packed16[kNets];
@@ -164,9 +156,7 @@ int state_check(const nav_td3_member* members, int32_t n_members, StateMember* d
                                        t.v_actor,     t.v_critic[0], t.v_critic[1]};
         StateMember e{};
         for (int i = 0; i < kNets; ++i) {
-            if (!same_shape(*nets[i], *nets0[i]) || !aligned16(nets[i]->params) ||
-                !aligned16(moments[i]))
-                return NAV_EINVAL;
+            if (!aligned16(nets[i]->params) || !aligned16(moments[i])) return NAV_EINVAL;
             if (packed16[i] && !aligned16(nets[i]->packed)) return NAV_EINVAL;
             e.seg[i] = reinterpret_cast<uint4*>(nets[i]->params);
             e.units[i] = params16[i];
@@ -176,7 +166,7 @@ int state_check(const nav_td3_member* members, int32_t n_members, StateMember* d
             e.seg[2 * kNets + i] = reinterpret_cast<uint4*>(moments[i]);
             e.units[2 * kNets + i] = params16[i % 3];
         }
-        if (t.replay.capacity != cap || !aligned16(t.replay.rows)) return NAV_EINVAL;
+        if (!aligned16(t.replay.rows)) return NAV_EINVAL;
         e.seg[kRing] = reinterpret_cast<uint4*>(t.replay.rows);
         e.units[kRing] = cap * 2;  // 32-byte rows
         if (dst) dst[m] = e;
@@ -185,6 +175,20 @@ int state_check(const nav_td3_member* members, int32_t n_members, StateMember* d
 }
 
 }  // namespace
+
+int navi_table_write(const void* host, int64_t bytes, void* dev, hipStream_t st) {
+    const uint32_t* words = static_cast<const uint32_t*>(host);
+    const int64_t total = bytes / 4;
+    for (int64_t at = 0; at < total; at += kChunkWords) {
+        StateChunk c;
+        const int n = (int)(total - at < kChunkWords ? total - at : kChunkWords);
+        for (int i = 0; i < n; ++i) c.w[i] = words[at + i];
+        hipLaunchKernelGGL(k_state_chunk_write, dim3(1), dim3(kBlock), 0, st, c,
+                           static_cast<uint32_t*>(dev) + at, n);
+        NAV_CHECK_LAUNCH();
+    }
+    return 0;
+}
 
 extern "C" {
 
@@ -209,27 +213,12 @@ int nav_td3_pop_state_build(const nav_td3_member* members, int32_t n_members, vo
     if (!state_table || n_members < 1 || n_members > kMaxMembers) return NAV_EINVAL;
     StateMember* host = static_cast<StateMember*>(calloc((size_t)n_members, sizeof(StateMember)));
     if (!host) return NAV_EINVAL;
-    const int rc = state_check(members, n_members, host);
-    if (rc) {
-        free(host);
-        return rc;
-    }
-    const uint32_t* words = reinterpret_cast<const uint32_t*>(host);
-    const int64_t total = (int64_t)n_members * (int64_t)(sizeof(StateMember) / 4);
-    for (int64_t at = 0; at < total; at += kChunkWords) {
-        StateChunk c;
-        const int n = (int)(total - at < kChunkWords ? total - at : kChunkWords);
-        for (int i = 0; i < n; ++i) c.w[i] = words[at + i];
-        hipLaunchKernelGGL(k_state_chunk_write, dim3(1), dim3(kBlock), 0, S(stream), c,
-                           static_cast<uint32_t*>(state_table) + at, n);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            free(host);
-            return -(int)e;
-        }
-    }
+    int rc = state_check(members, n_members, host);
+    if (!rc)
+        rc = navi_table_write(host, (int64_t)n_members * (int64_t)sizeof(StateMember), state_table,
+                              S(stream));
     free(host);
-    return 0;
+    return rc;
 }
 
 int nav_td3_pop_exploit(const nav_td3_member* members, int32_t n_members,

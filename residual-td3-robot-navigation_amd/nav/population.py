@@ -62,6 +62,22 @@ PBT_EXPLORE_KEYS = PBT_PARAM_KEYS | PBT_TD3_KEYS
 PBT_FACTORS = (0.8, 1.25)
 
 
+def state_member(t, ring):
+    """Learner t's state as a nav_td3_member: the six networks, the Adam moments and the replay
+    ring; every other field stays null."""
+    m = NavTd3Member()
+    m.actor, m.target_actor = t.actor_network.desc(), t.target_actor.desc()
+    m.critics[0], m.critics[1] = t.critic_network_1.desc(), t.critic_network_2.desc()
+    m.target_critics[0] = t.target_critic_network_1.desc()
+    m.target_critics[1] = t.target_critic_network_2.desc()
+    m.replay = ring.desc()
+    oa, oc1, oc2 = t.actor_optimizer, t.critic_optimizer_1, t.critic_optimizer_2
+    m.m_actor, m.v_actor = oa.m.data_ptr(), oa.v.data_ptr()
+    m.m_critic[0], m.m_critic[1] = oc1.m.data_ptr(), oc2.m.data_ptr()
+    m.v_critic[0], m.v_critic[1] = oc1.v.data_ptr(), oc2.v.data_ptr()
+    return m
+
+
 def default_fitness(score):
     """Higher is better: the success rate, then the smaller mean best distance."""
     return (score["success_rate"], -score["mean_best_distance"])
@@ -224,18 +240,10 @@ class PopulationLearner:
         self.rebuild(stream)
 
     def _member(self, t, ring, inj):
+        """state_member's fields, then the learner's hyper-parameters and workspace."""
         c = t.cfg
-        m = NavTd3Member()
-        m.actor, m.target_actor = t.actor_network.desc(), t.target_actor.desc()
-        m.critics[0], m.critics[1] = t.critic_network_1.desc(), t.critic_network_2.desc()
-        m.target_critics[0] = t.target_critic_network_1.desc()
-        m.target_critics[1] = t.target_critic_network_2.desc()
-        m.replay = ring.desc()
-        oc1, oc2, oa = self._opts(t)
-        m.m_actor, m.v_actor = oa.m.data_ptr(), oa.v.data_ptr()
-        m.m_critic[0], m.m_critic[1] = oc1.m.data_ptr(), oc2.m.data_ptr()
-        m.v_critic[0], m.v_critic[1] = oc1.v.data_ptr(), oc2.v.data_ptr()
-        m.actor_lr, m.critic_lr = oa.lr, oc1.lr
+        m = state_member(t, ring)
+        m.actor_lr, m.critic_lr = t.actor_optimizer.lr, t.critic_optimizer_1.lr
         m.policy_noise, m.noise_clip, m.max_action = c.policy_noise, c.noise_clip, c.max_action
         m.gamma, m.tau = c.gamma, c.tau
         m.seed_lo, m.seed_hi = t.seed & 0xFFFFFFFF, (t.seed >> 32) & 0xFFFFFFFF
@@ -492,27 +500,14 @@ class PopulationTrainer:
             res.append(d)
         return res
 
-    def _state_member(self, m):
-        """Member m's learner state as a nav_td3_member: the six networks, the moments and the
-        ring; everything else stays null (nav_td3_pop_exploit neither reads nor writes it)."""
-        t, e = self.td3[m], NavTd3Member()
-        e.actor, e.target_actor = t.actor_network.desc(), t.target_actor.desc()
-        e.critics[0], e.critics[1] = t.critic_network_1.desc(), t.critic_network_2.desc()
-        e.target_critics[0] = t.target_critic_network_1.desc()
-        e.target_critics[1] = t.target_critic_network_2.desc()
-        e.replay = self.rings[m].desc()
-        oa, oc1, oc2 = t.actor_optimizer, t.critic_optimizer_1, t.critic_optimizer_2
-        e.m_actor, e.v_actor = oa.m.data_ptr(), oa.v.data_ptr()
-        e.m_critic[0], e.m_critic[1] = oc1.m.data_ptr(), oc2.m.data_ptr()
-        e.v_critic[0], e.v_critic[1] = oc1.v.data_ptr(), oc2.v.data_ptr()
-        return e
-
     def state_table(self, stream=None, rebuild=False):
         """(the nav_td3_member array, the device table) of the members' learner state, built on
         first use and kept: the networks, moments and rings change in place. rebuild=True after
         a buffer was replaced."""
         if self._state is None or rebuild:
-            arr = (NavTd3Member * self.P)(*[self._state_member(m) for m in range(self.P)])
+            # (nav_td3_pop_exploit neither reads nor writes what state_member leaves null)
+            arr = (NavTd3Member * self.P)(*[state_member(t, r)
+                                            for t, r in zip(self.td3, self.rings)])
             tab = torch.zeros(lib().nav_td3_pop_state_bytes(self.P), dtype=torch.uint8,
                               device=self.device)
             lib().nav_td3_pop_state_build(arr, self.P, ptr(tab), stream_handle(stream))

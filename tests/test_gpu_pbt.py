@@ -232,6 +232,45 @@ def test_exploit_is_a_byte_copy_and_touches_nothing_else(nav, hidden, nh):
     equal_tree(copied_state(td3[0]), before[1], "member 0 is member 1")
 
 
+def test_state_table_past_one_chunk(nav):
+    """Seven distinct learners at hidden 32 x 1, batch 64, after one epoch: the smallest
+    population whose state table (7 entries of 304 B) spans two of the table writer's 2 KB chunks,
+    the second one partial and member 6's entry across the boundary. src = [0, 1], dst = [6, 5],
+    3 000 ring rows: members 6 and 5 are byte copies of members 0 and 1, the others are
+    untouched."""
+    from nav._lib import NavTd3Member, lib, ptr, stream_handle
+    P, B = 7, 64
+    rings = [make_ring(m) for m in range(P)]
+    td3 = [make_td3(m, 32, 1, B, 1) for m in range(P)]
+    for t, r in zip(td3, rings):
+        t.td3_update(r, 1)
+    torch.cuda.synchronize()
+    before = [copied_state(t) for t in td3]
+    rows0 = [r.rows.clone() for r in rings]
+    for a in range(P):  # a condition of the test: every copied buffer differs between members
+        for b in range(a + 1, P):
+            same = [p for (p, x), (_, y) in zip(leaves(before[a]), leaves(before[b]))
+                    if torch.equal(x, y) and not p.startswith("/packed")]
+            assert not same, (a, b, same)
+            assert not torch.equal(rows0[a][:FILL], rows0[b][:FILL])
+    L, s = lib(), stream_handle()
+    arr = (NavTd3Member * P)(*[state_member(t, r) for t, r in zip(td3, rings)])
+    nbytes = L.nav_td3_pop_state_bytes(P)
+    assert nbytes > 2048 and nbytes % 2048 != 0
+    tab = torch.zeros(nbytes, dtype=torch.uint8, device=DEV)
+    L.nav_td3_pop_state_build(arr, P, ptr(tab), s)
+    i32 = lambda v: (C.c_int32 * len(v))(*v)  # noqa: E731
+    L.nav_td3_pop_exploit(arr, P, ptr(tab), i32([0, 1]), i32([6, 5]), 2, FILL, s)
+    torch.cuda.synchronize()
+    for d, src in ((6, 0), (5, 1)):
+        equal_tree(copied_state(td3[d]), before[src], f"member {d} is member {src}")
+        assert torch.equal(rings[d].rows[:FILL], rows0[src][:FILL])
+        assert torch.equal(rings[d].rows[FILL:], rows0[d][FILL:])
+    for m in range(5):
+        equal_tree(copied_state(td3[m]), before[m], f"member {m} untouched")
+        assert torch.equal(rings[m].rows, rows0[m])
+
+
 # ---- 3 .. 6. the trainer
 SOA = ("state", "goal", "region", "hist", "meta", "plan_index", "path_length", "episodes",
        "noise_scale")

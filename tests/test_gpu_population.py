@@ -224,6 +224,62 @@ def test_tick_identical_members(nav):
         assert torch.equal(got_end[k], end[k]), k
 
 
+def test_tick_table_past_one_chunk(nav):
+    """P = 7 x 64 envs at hidden 32 x 1: the smallest population whose table (7 entries of 296 B)
+    spans two of the table writer's 2 KB chunks, the second one partial and member 6's entry
+    across the boundary. Distinct actors and constants, 8 ticks with demos, rings of 3 x 64 rows:
+    as test_tick_distinct_members, member m's slice of every output and its ring rows equal the
+    single-policy run with actor m and params m."""
+    from nav.population import PopulationTable
+    from nav.vec_env import ReplayRing
+    P7, epm, ticks = 7, 64, 8
+    n = P7 * epm
+    env = make_env(n, True)
+    start = snapshot(env)
+    actors = [make_actor(32, 1, 31 + m) for m in range(P7)]
+    params = [member_params(m % 3, demo_factor=10.0 + 5.0 * m) for m in range(P7)]
+    cap = 3 * epm
+    ring_rows = torch.zeros(P7, cap, 8, dtype=torch.float32, device=DEV)
+    rings = [ReplayRing(cap, DEV, rows=ring_rows[m]) for m in range(P7)]
+    pop = PopulationTable(actors, params, rings, epm)
+    assert pop.table.numel() > 2048 and pop.table.numel() % 2048 != 0
+
+    def pop_tick(t, action, reward):
+        base = rings[0].position
+        env.act_tick_pop(pop, t, base, action_out=action, reward_out=reward)
+        for r in rings:
+            r.advance(epm)
+        slots = (base + torch.arange(epm, device=DEV)) % cap
+        return {"rows": ring_rows[:, slots].clone()}
+
+    got = run_ticks(env, ticks, pop_tick)
+    got_end = snapshot(env)
+    ends = []
+    for m in range(P7):
+        restore(env, start)
+        env.p = params[m]
+        ring = ReplayRing(ticks * n, DEV)
+
+        def ref_tick(t, action, reward):
+            env.act_tick(actors[m], t, ring, action_out=action, reward_out=reward)
+
+        rec = run_ticks(env, ticks, ref_tick)
+        rows = ring.rows.view(ticks, n, 8)
+        for t in range(ticks):
+            for k in STEP_OUT + ("action", "reward"):
+                assert torch.equal(member_view(k, got[t][k], m, epm),
+                                   member_view(k, rec[t][k], m, epm)), (k, t, m)
+            assert torch.equal(got[t]["rows"][m], rows[t, m * epm:(m + 1) * epm]), ("rows", t, m)
+        end = snapshot(env)
+        for k in SOA:
+            assert torch.equal(member_view(k, got_end[k], m, epm),
+                               member_view(k, end[k], m, epm)), (k, m)
+        ends.append(end)
+    # a condition on the inputs: the members' runs differ, the last one's too
+    assert not torch.equal(ends[0]["state"], ends[6]["state"])
+    assert not torch.equal(ends[5]["state"], ends[6]["state"])
+
+
 def random_starts(env, seed):
     """test_gpu_test_rollout.py's form: uniform starts in the world; every 5th env one unit from
     its goal, so that some rows stop at the first step while their workgroup goes on."""

@@ -140,9 +140,17 @@ def _n_mismatch(a):
     a.env.n = P * EPM + 64
 
 
+def _n_members(n):  # (the env count follows, so that the member count alone is at fault)
+    def f(a):
+        a.n_members, a.env.n = n, n * EPM
+    return f
+
+
 # (case, alteration, entry points it applies to)
 ALL, TICK, RINGS = ("build", "tick", "test"), ("tick",), ("build", "tick")
 CASES = [
+    ("no members", _n_members(0), ALL),
+    ("257 members", _n_members(257), ALL),
     ("envs_per_member not a multiple of 64", _epm_not_64, ALL),
     ("envs_per_member not a multiple of envs_per_group", _epm_not_epg, TICK),
     ("d_in differs", _set("d_in", 1, 4), ALL),

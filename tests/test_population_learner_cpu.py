@@ -111,9 +111,11 @@ BAD = [
     ("B = 0", _set("B", 0), ALL),
     ("no table", _set("table", None), ALL),
     ("another hidden width", _net_field("actor", "hidden", 32), ALL),
+    ("another padded width", _net_field("target_actor", "hidden_pad", 96), ALL),
     ("another depth", _net_field("critics", "n_hidden", 2, 1), ALL),
+    ("another target depth", _net_field("target_critics", "n_hidden", 2, 0, m=2), ALL),
     ("another critic input", _net_field("critics", "d_in", 3, 0, m=0), ALL),
-    ("another ring capacity", _capacity, ROWS),
+    ("another ring capacity", _capacity, ALL),
     ("size = 0", _set("size", 0), ("critic", "actor")),
     ("size > capacity", _set("size", CAP + 1), ("critic", "actor")),
     ("no ring rows", lambda a: setattr(a.m[1].replay, "rows", None), ROWS),

@@ -17,7 +17,7 @@ for u in $2; do
   case $u in
     learner) units="$units learner_kernels" ;;
     env) units="$units env_kernels" ;;
-    mlp0) units="$units mlp_kernels" ;;
+    mlp0) units="$units mlp_abi" ;;
     mlp[1-8]) units="$units mlp_nt${u#mlp}" ;;
     mlp8agpr) units="$units mlp_nt8"; plain=1 ;;
     *) echo "unit?"; exit 2 ;;

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Compile a .hip file to gfx950 assembly and print per-kernel register / scratch / instruction
 # counts for kernels whose mangled name matches $2 (grep -E pattern).
-# usage: tools/isa_stats.sh residual-td3-robot-navigation_amd/csrc/mlp_kernels.hip 'k_mlp_fwdILi8ELi2'
+# usage: tools/isa_stats.sh residual-td3-robot-navigation_amd/csrc/learner_kernels.hip 'k_wgrad_fact'
 set -eu
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 SRC=$1
