@@ -13,14 +13,16 @@ import mlp_ref as R
 N_DEMO = 37   # demonstration rows behind epoch_case's ring of R.RING rows
 
 
-def bc_case(hidden, nh, B, b_demo):
+def bc_case(hidden, nh, B, b_demo, K=None):
     """mlp_ref.epoch_case with a demonstration tail: N_DEMO more rows of the ring's own kind
     (random rows, done = 0) behind it, and actor sample indices whose first b_demo entries
-    address the tail."""
-    case = R.epoch_case(hidden, nh, B)
+    address the tail. K: epoch_case's joint rescaling (the tail's reward column by 2^K as well)."""
+    case = R.epoch_case(hidden, nh, B, K)
     g = torch.Generator().manual_seed(7000 + B + nh + b_demo)
     tail = torch.randn(N_DEMO, 8, generator=g) * 10
     tail[:, 7] = 0.0
+    if K is not None:
+        tail[:, 4] = R.ldexp32(tail[:, 4], K)
     rows = torch.cat([case["rows"], tail], 0).contiguous()
     idx_a = case["idx_a"].clone()
     idx_a[:b_demo] = R.RING + torch.randint(0, N_DEMO, (b_demo,), generator=g)

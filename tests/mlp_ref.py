@@ -277,14 +277,20 @@ def pad32(hidden):
     return (hidden + 31) // 32 * 32
 
 
-def chain_case(d_in, d_out, hidden, nh, M):
-    """The net and rows of unfused_chain_run, on the CPU: (layers, x, dy)."""
+def chain_case(d_in, d_out, hidden, nh, M, shift=None):
+    """The net and rows of unfused_chain_run, on the CPU: (layers, x, dy). shift = (a, ks, g):
+    the same case rescaled by powers of two (shift_layers; x by 2^a, dy by 2^g)."""
     from oracle.td3_oracle import make_mlp_params
     p = make_mlp_params(17, [d_in] + [hidden] * nh + [d_out])
     g = torch.Generator().manual_seed(2000 + M + nh)
     x = (torch.randn(M, d_in, generator=g) * 20).contiguous()
     dy = torch.randn(M, d_out, generator=g) / M
-    return [(torch.tensor(W), torch.tensor(b)) for W, b in p], x, dy
+    layers = [(torch.tensor(W), torch.tensor(b)) for W, b in p]
+    if shift is not None:
+        a, ks, gs = shift
+        layers, _ = shift_layers(layers, a, ks)
+        x, dy = ldexp32(x, a).contiguous(), ldexp32(dy, gs)
+    return layers, x, dy
 
 
 def chain_quantities(c, nh):
@@ -300,10 +306,12 @@ EPOCH_SEEDS = dict(ta=61, tc0=62, tc1=63, cr0=64, cr1=65, actor=66, atgt=67)
 RING = 500
 
 
-def epoch_case(hidden, nh, B):
+def epoch_case(hidden, nh, B, K=None):
     """A TD3 epoch's inputs on the CPU: a ring of 500 random rows (done ~ 10 %), injected sample
     indices of the critic and the actor phase, smoothing noise, and the layers of seven distinct
-    nets (target actor, target critics, online critics, actor, the actor's own target)."""
+    nets (target actor, target critics, online critics, actor, the actor's own target).
+    K: the joint rescaling of joint_shifts (every critic's layers by shifts of total K, every
+    actor's by shifts of total 0, the ring's reward column by 2^K)."""
     from oracle.td3_oracle import make_mlp_params
     g = torch.Generator().manual_seed(9000 + B + nh)
     rows = torch.randn(RING, 8, generator=g) * 10
@@ -316,6 +324,12 @@ def epoch_case(hidden, nh, B):
         d_in, d_out = (2, 2) if name in ("ta", "actor", "atgt") else (4, 1)
         p = make_mlp_params(seed, [d_in] + [hidden] * nh + [d_out])
         layers[name] = [(torch.tensor(W), torch.tensor(b)) for W, b in p]
+    if K is not None:
+        ks_actor, ks_critic = joint_shifts(nh, K)
+        rows[:, 4] = ldexp32(rows[:, 4], K)
+        for name in layers:
+            ks = ks_actor if name in ("ta", "actor", "atgt") else ks_critic
+            layers[name], _ = shift_layers(layers[name], 0, ks)
     return dict(rows=rows, idx=idx, idx_a=idx_a, eps=eps, layers=layers, B=B, hidden=hidden,
                 nh=nh)
 
@@ -404,15 +418,22 @@ def actor_epoch(actor, critic, batch, bits_a, bits_c, dtype=torch.float64, narro
 
 
 # ---- the unfused launches: forward -> row backward -> weight gradients -> reduce ----
-def unfused_chain_run(d_in, d_out, hidden, nh, M, splits=5, nan_fill=False):
+def unfused_chain_run(d_in, d_out, hidden, nh, M, splits=5, nan_fill=False, shift=None,
+                      case=None):
     """nav_mlp_forward -> nav_mlp_backward (every dz row saved) -> nav_mlp_wgrad -> nav_grad_reduce
     of a make_mlp_params(17) net on randn * 20 rows from manual_seed(2000 + M + nh). nan_fill: the
-    edge slabs, the weight-gradient slabs and the flat gradient start as NaN. Returns dict(net,
-    layers, x, dy, out, acts, dz, dx, grad (CPU tensors), bits)."""
+    edge slabs, the weight-gradient slabs and the flat gradient start as NaN. shift = (a, ks, g):
+    chain_case's rescaled case; case = (layers, x, dy): those instead. Returns dict(net, layers,
+    x, dy, out, acts, dz, dx, grad (CPU tensors), bits, masks)."""
     from nav._lib import descs, lib, parr, ptr, stream_handle
-    from nav.mlp import forward
-    net, layers = make_net(d_in, d_out, hidden, nh, 17)
-    _, x, dy = chain_case(d_in, d_out, hidden, nh, M)
+    from nav.mlp import DeviceMLP, forward
+    if shift is None and case is None:
+        net, layers = make_net(d_in, d_out, hidden, nh, 17)
+        _, x, dy = chain_case(d_in, d_out, hidden, nh, M)
+    else:
+        layers, x, dy = case if case is not None else chain_case(d_in, d_out, hidden, nh, M, shift)
+        net = DeviceMLP(d_in, d_out, hidden, nh, DEV).load(
+            [(W.numpy(), b.numpy()) for W, b in layers])
     xd, dyd = x.to(DEV), dy.to(DEV)
     out = torch.zeros(M, d_out, device=DEV)
     acts = torch.zeros(nh, M, net.hp, device=DEV)
@@ -434,7 +455,8 @@ def unfused_chain_run(d_in, d_out, hidden, nh, M, splits=5, nan_fill=False):
     L.nav_grad_reduce(C.byref(net.desc()), ptr(hs), splits, ptr(eslab), nblk, ptr(grad), s)
     torch.cuda.synchronize()
     return dict(net=net, layers=layers, x=x, dy=dy, out=out.cpu(), acts=acts.cpu(), dz=dz.cpu(),
-                dx=dx.cpu(), grad=grad.cpu(), bits=relu_bits(masks, nh, net.hp, hidden, M))
+                dx=dx.cpu(), grad=grad.cpu(), bits=relu_bits(masks, nh, net.hp, hidden, M),
+                masks=masks.cpu())
 
 
 def split_gemm_row_errors(d_in, d_out, hidden, nh, M, splits=5, detail=False):
@@ -533,3 +555,162 @@ def _assert_images_exact(net, tag):
             rec = (P[0].double() + P[1].double()) / sc
             tol = 2.0 ** -22 * cmax.double() + 1e-45
             assert ((rec - Bk.double()).abs() <= tol).all(), (tag, L, which)
+
+
+# ---- exact rescaling by powers of two ----
+# Inputs by 2^a, layer l's weights by 2^k_l and its bias by 2^(a + k_0 + .. + k_l), the incoming
+# gradient by 2^g: while nothing leaves the normal f32 range, every f32 chain of the rescaled case
+# yields the base case's values times a known power of two, bit for bit (a power of two commutes
+# with every rounding). The kernels' scale bookkeeping must do the same.
+SHIFT_SETS = {"S1": (7, (20, -35, 15), -9), "S2": (-30, (-12, -11, -10), 25),
+              "S3": (40, (10, 10, 10), -60)}
+SHIFT_LO, SHIFT_HI, SHIFT_CAP = 2.0 ** -100, 2.0 ** 100, 1e-3
+
+
+def ldexp32(t, k):
+    """t 2^k in f32 (exact while the result is a normal float or 0)."""
+    return (t.double() * 2.0 ** k).to(t.dtype)
+
+
+def layer_ks(ks, nh, fill=3):
+    """ks truncated or extended to the nh + 1 layers; a fourth or later layer takes `fill`."""
+    ks = tuple(ks)[:nh + 1]
+    return ks + (fill,) * (nh + 1 - len(ks))
+
+
+def shift_set(name, nh):
+    """(a, ks, g) of shift set `name` for a net of nh hidden layers."""
+    a, ks, g = SHIFT_SETS[name]
+    return a, layer_ks(ks, nh), g
+
+
+def shift_layers(layers, a, ks):
+    """(layers', cums): W_l' = W_l 2^k_l, b_l' = b_l 2^cums[l + 1], cums[0] = a, cums[l + 1] =
+    cums[l] + k_l (the exponent h_l carries, and the output for l = n_hidden)."""
+    assert len(ks) == len(layers)
+    cums = [a]
+    out = []
+    for (W, b), k in zip(layers, ks):
+        cums.append(cums[-1] + k)
+        out.append((ldexp32(W, k), ldexp32(b, cums[-1])))
+    return out, cums
+
+
+def expected_shifts(a, ks, g):
+    """The exponent every quantity of the rescaled chain carries over the base chain's, by
+    quantity name: out, h_l, dz_l, dx, dW_l, db_l (l as in chain_quantities)."""
+    nh = len(ks) - 1
+    cums = [a]
+    for k in ks:
+        cums.append(cums[-1] + k)
+    s = dict(out=cums[nh + 1], dx=g + sum(ks))
+    for l in range(nh):
+        s[f"h{l}"] = cums[l + 1]
+        s[f"dz{l}"] = g + sum(ks[l + 1:])
+    for l in range(nh + 1):
+        dzl = s[f"dz{l}"] if l < nh else g
+        s[f"dW{l}"], s[f"db{l}"] = dzl + cums[l], dzl
+    return s
+
+
+def joint_shifts(nh, K):
+    """(ks_actor, ks_critic) of the fused epochs' joint rescaling: the actor's layer shifts (S1's,
+    the last one adjusted) sum to 0, so actions keep their magnitude; the critic's are the same
+    with K added to the third layer's (or to the last of a shallower net), total K."""
+    ks = list(layer_ks(SHIFT_SETS["S1"][1], nh))
+    ks[-1] -= sum(ks)
+    kc = list(ks)
+    kc[min(2, nh)] += K
+    return tuple(ks), tuple(kc)
+
+
+def assert_shifted(got, base, s, name, lo=SHIFT_LO, hi=SHIFT_HI):
+    """got == base 2^s bit for bit on every entry whose base value is 0 or whose shifted
+    magnitude lies in [lo, hi] = [2^-100, 2^100]; the entries outside that window (where a
+    subnormal or an overflow may legitimately round) are left out, and must be at most 1e-3 of
+    the non-zero ones. Returns that share."""
+    import math
+    assert got.shape == base.shape, (name, got.shape, base.shape)
+    got, base = got.reshape(-1), base.reshape(-1)
+    want = base.double() * 2.0 ** s
+    mag = want.abs()
+    nz = base != 0
+    held = ~nz | ((mag >= lo) & (mag <= hi))
+    n_nz = int(nz.sum())
+    share = float((~held).sum()) / n_nz if n_nz else 0.0
+    assert share <= SHIFT_CAP, f"{name}: {share:.2e} of the non-zero entries leave the window"
+    bad = held & ~(got.double() == want)
+    n_bad = int(bad.sum())
+    if n_bad:
+        i = int(bad.nonzero()[0])
+        g_, b_ = float(got[i]), float(base[i])
+        if b_ != 0 and g_ != 0 and math.isfinite(g_):
+            m, e = math.frexp(g_ / b_)
+            ratio = f"got / base = {m * 2:.9g} * 2^{e - 1}"
+        else:
+            ratio = "got / base undefined"
+        raise AssertionError(
+            f"{name}: {n_bad} of {int(held.sum())} entries differ from base * 2^{s}; first at "
+            f"{i}: got {g_!r} base {b_!r} ({ratio}, expected 2^{s})")
+    return share
+
+
+# ---- the cases of the rescaling tests (tests/test_scale_cpu.py, tests/test_gpu_scale.py) ----
+SCALE_BIG = 16421  # 64-row blocks: gemm_cols_step and its per-step A scale
+# (d_in, d_out, hidden, nh), one per code path: k_wgrad_fact<8> / <4> / <2> with gemm_bits, the
+# operand-form k_wgrad, k_wgrad_gen at a padded width, gemm_bits under a padded hp = 96, and a
+# net without a hidden x hidden product
+SCALE_SHAPES = [(4, 1, 256, 2), (4, 1, 128, 2), (4, 1, 64, 2), (2, 2, 256, 2), (2, 2, 200, 3),
+                (4, 1, 90, 3), (4, 1, 24, 1)]
+SCALE_CHAIN_CASES = [(s, 97) for s in SCALE_SHAPES] + [((4, 1, 256, 2), SCALE_BIG),
+                                                       ((2, 2, 256, 2), SCALE_BIG)]
+# the fused epochs: (hidden, nh, B), each at K = -24 and K = +18 (joint_shifts)
+SCALE_EPOCH_CASES = [(256, 2, SCALE_BIG), (256, 2, 100), (200, 3, 100), (64, 2, 100)]
+SCALE_KS = (-24, 18)
+# the ends of the range (held to the fp64 bars, not to bit equality: clamps and caps may bind)
+RANGE_SHAPES = [(4, 1, 256, 2), (2, 2, 256, 2), (2, 2, 200, 3)]
+RANGE_CASES = [(r, s, 97) for r in ("R1", "R2", "R3", "R4", "R5") for s in RANGE_SHAPES]
+RANGE_CASES += [(r, (4, 1, 256, 2), SCALE_BIG) for r in ("R1", "R3")]
+ZERO_X_ROWS, ZERO_DY_ROWS, ZERO_W_ROW, ZERO_W_COL = slice(32, 64), slice(64, 96), 5, 9
+
+
+def range_shift(name, nh):
+    """(a, ks, g) of the range ends R1 .. R4: R1 small hidden weights (k_1 = -118, the output
+    layer +118: the image's column exponents clamp at 126), R2 large activations (a = +60, k_0 =
+    +40, k_1 = -100: h_0 near 2^100), R3 tiny gradients (g = -110), R4 large gradients (g = +70,
+    the output layer +20)."""
+    ks = [0] * (nh + 1)
+    a = g = 0
+    if name == "R1":
+        ks[1], ks[nh] = ks[1] - 118, ks[nh] + 118
+    elif name == "R2":
+        a, ks[0], ks[1] = 60, 40, ks[1] - 100
+    elif name == "R3":
+        g = -110
+    elif name == "R4":
+        g, ks[nh] = 70, 20
+    else:
+        raise KeyError(name)
+    return a, tuple(ks), g
+
+
+def range_case(name, d_in, d_out, hidden, nh, M):
+    """(layers, x, dy) of a range end: chain_case under range_shift, or R5, the zeros: one whole
+    32-row tile of x all zero under zero biases, one row and one column of the first hidden x
+    hidden weight all zero (an all-zero column of its forward and of its backward image), dy all
+    zero in another 32-row tile."""
+    if name != "R5":
+        return chain_case(d_in, d_out, hidden, nh, M, range_shift(name, nh))
+    layers, x, dy = chain_case(d_in, d_out, hidden, nh, M)
+    layers = [(W.clone(), torch.zeros_like(b)) for W, b in layers]
+    layers[1][0][ZERO_W_ROW, :] = 0
+    layers[1][0][:, ZERO_W_COL] = 0
+    x, dy = x.clone(), dy.clone()
+    x[ZERO_X_ROWS] = 0
+    dy[ZERO_DY_ROWS] = 0
+    return layers, x, dy
+
+
+def forward_signs(layers, x, dtype=torch.float32):
+    """The ReLU decisions of a torch-CPU forward at `dtype` (for chains without a device)."""
+    return [z > 0 for z in mlp_forward(layers, x, dtype)[1]]
