@@ -1,5 +1,5 @@
 // mlp_common.h — the device MLP layout (include/navenv.h nav_mlp) and the fragment helpers
-// shared by the row kernels (mlp_rows.h) and the learner kernels (learner_kernels.hip).
+// shared by the row kernels (mlp_rows.h) and the learner kernels (wgrad.h, reduce_adam.h).
 #pragma once
 #include <stdlib.h>
 
@@ -8,9 +8,9 @@
 using namespace nav;
 
 // The population learner's table (nav_td3_pop_table_build) is [n_members] row-kernel arguments
-// (mlp_rows.h) followed by [n_members] entries of the cross-row kernels
-// (learner_kernels.hip built with NAV_LEARNER_POP): that object's size and its check + fill of
-// members' entries into host memory `dst` (NULL: check only), called by the table's entry points.
+// (mlp_rows.h) followed by [n_members] entries of the cross-row kernels (learner_pop.hip): that
+// object's entry size and its check + fill of members' entries into host memory `dst` (NULL:
+// check only), called by the table's entry points.
 int64_t navi_learner_pop_entry_bytes();
 int64_t navi_rows_pop_entry_bytes();  // (mlp_abi.hip's, a multiple of 8)
 int navi_learner_pop_fill(const nav_td3_member* members, int32_t n_members, int64_t B,

@@ -13,7 +13,7 @@
 // <= 4) and the bias run on f32 MFMA (layer0_unit's fma chain bit for bit), the output layer (N =
 // 1 or 2) on the VALU with a lane-transpose reduce; ReLU derivatives travel from forward to
 // backward as C-layout bit masks. The cross-row weight
-// gradients and the reduce + Adam are learner_kernels.hip. The per-width launchers are
+// gradients and the reduce + Adam are wgrad.h and reduce_adam.h. The per-width launchers are
 // mlp_rows_nt.hip, the C ABI is mlp_abi.hip: nothing host-side here but sizes and argument
 // structs.
 #pragma once

@@ -350,6 +350,35 @@ def test_fused_reduce_adam_and_polyak_multi_bitwise(nav):
             assert torch.equal(t1.params, t2.params) and torch.equal(t1.packed, t2.packed)
 
 
+@pytest.mark.parametrize("nblk", [19, 300])  # the 16-step tail loop alone; one 256-stride trip + tail
+@pytest.mark.parametrize("nh,splits", [(2, 5), (1, 0)])
+def test_grad_reduce_multi_equals_two_single_reduces(nav, nh, splits, nblk):
+    """nav_grad_reduce_multi on the twin critics writes, byte for byte, what one nav_grad_reduce
+    per critic writes (the single form is pinned against the reference sum above). The slabs are
+    seeded random floats. 5 splits: one of the 4 split-group lanes sums two slabs; 1 hidden layer:
+    no hidden slabs (NULL entries, splits 0)."""
+    from nav._lib import descs, lib, parr, ptr, stream_handle
+    L = lib()
+    s = stream_handle()
+    nets = [make_net(4, 1, 64, nh, 70 + k)[0] for k in range(2)]
+    gen = torch.Generator(device=DEV).manual_seed(1234 + nblk)
+    hc, ec = L.nav_mlp_hidden_count(64, nh), L.nav_mlp_edge_count(4, 1, 64, nh)
+    hs = [torch.randn(splits, hc, device=DEV, generator=gen) if nh > 1 else None for _ in range(2)]
+    es = [torch.randn(nblk, ec, device=DEV, generator=gen) for _ in range(2)]
+    g_multi = [torch.full((n.count,), float("nan"), device=DEV) for n in nets]
+    g_single = [torch.full((n.count,), float("nan"), device=DEV) for n in nets]
+    L.nav_grad_reduce_multi(descs(*nets), 2, parr(*hs), splits, parr(*es), nblk, parr(*g_multi), s)
+    for k in range(2):
+        L.nav_grad_reduce(C.byref(nets[k].desc()), ptr(hs[k]), splits, ptr(es[k]), nblk,
+                          ptr(g_single[k]), s)
+    torch.cuda.synchronize()
+    for k in range(2):
+        a, b = g_multi[k].view(torch.int32), g_single[k].view(torch.int32)
+        assert torch.equal(a, b)
+        assert bool(torch.isfinite(g_multi[k]).all())  # every entry of the gradient was written
+    assert not torch.equal(g_multi[0], g_multi[1])
+
+
 def test_td3_update_vs_oracle_and_reference(nav):
     """TD3.td3_update (robot.py:258-398) with the reference golden's weights, batches and noise:
     losses and post-update parameters vs the oracle (and the reference's own digests)."""
