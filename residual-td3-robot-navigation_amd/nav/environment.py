@@ -96,6 +96,12 @@ class Environment:
 
     # ---- environment.py:122-127: returns the committed state object (unchanged object if not)
     def step(self, action):
+        # environment.py:125 tests the dynamics' own result, which the clip of line 117 keeps in
+        # range unless it is NaN (a NaN action): then the caller gets the unchanged object back.
+        # nav_env_step's output is the committed state, never NaN, so it cannot tell
+        raw = self.dynamics(np.asarray(self.robot_state, np.float64), action)
+        if not (0 <= raw[0] < K.WORLD_SIZE and 0 <= raw[1] < K.WORLD_SIZE):
+            return self.robot_state
         self._state.copy_(torch.from_numpy(np.asarray(self.robot_state, np.float64)[None]))
         self._a.copy_(torch.from_numpy(np.asarray(action, np.float64).reshape(1, 2)))
         nxt = torch.empty_like(self._state)

@@ -68,6 +68,30 @@ def test_demo_transitions_bit_equal_to_the_restatement(nav, n, T, frame):
         assert np.abs(got[:, 2:4].astype(np.float64) + got[:, 0:2]).max() <= 5.0 + 1e-4
 
 
+@pytest.mark.parametrize("case", range(4), ids=["trace", "trace_branches", "trace_branches_field",
+                                                 "hand"])
+def test_demo_transitions_vs_reference_pushes(nav, case):
+    """nav_demo_transitions (frame 0) on the demonstrations the reference drew against the rows
+    its process_demonstration pushed (the demo ticks of the three trace fixtures, 3 x 199 each,
+    and a hand-made path that ends inside the goal radius): state, action, next-state and done
+    columns equal, the reward equal or one float32 ulp from float32(push_r), rows inside
+    the goal radius exactly 50."""
+    from nav._lib import lib, params_struct, ptr, stream_handle
+    from test_oracle_branches_cpu import assert_demo_rows, demo_cases
+    name, st, ac, goals, want, rew = demo_cases()[case]
+    n, T = st.shape[:2]
+    rows = _nan(n * (T - 1), 8)
+    assert lib().nav_demo_transitions(
+        C.byref(params_struct()), n, T, ptr(torch.tensor(st, device=DEV)),
+        ptr(torch.tensor(ac, device=DEV)), ptr(torch.tensor(goals, device=DEV)), 0, ptr(rows),
+        stream_handle()) == 0
+    n_goal, n_ulp = assert_demo_rows(rows.cpu().numpy(), want, rew)
+    print(f"{name}: {n_goal} goal rows, {n_ulp} rewards one ulp off")
+    # a condition on the inputs: the goal-reward branch is taken (the field trace's CEM
+    # demonstrations never enter the radius; the hand-made path is there for that)
+    assert n_goal >= 2 or name == "trace_branches_field.npz"
+
+
 # ---- nav_td3_mix_idx ----
 MIX = dict(B=100, size=500, n_demo=37, demo_base=500, counter=3)
 

@@ -36,7 +36,9 @@ def test_environment_dynamics_and_step_api(navmods):
     d = golden("dynamics.npz")
     np.random.seed(0)
     env = environment.Environment(d["speed"], d["angle"])
-    for i in range(0, 300, 7):
+    # (136 .. 139: the fixture's NaN and infinite actions; only a NaN one is not committed)
+    assert d["committed"][136:140].tolist() == [0, 0, 1, 1]
+    for i in list(range(0, 300, 7)) + [136, 137, 138, 139]:
         out = env.dynamics(list(d["state"][i]), list(d["action"][i]))  # graphics.py:224 form
         ref = d["dynamics"][i]
         if np.isnan(ref).any():
@@ -57,10 +59,13 @@ def ulps_f32(a, b):
     return np.abs(a - b)
 
 
-def _trace_setup(environment, robot):
-    t = golden("trace.npz")
+TRACES = ["trace.npz", "trace_branches.npz", "trace_branches_field.npz"]
+
+
+def _trace_setup(environment, robot, name="trace.npz"):
+    t = golden(name)
     torch.manual_seed(0)
-    np.random.seed(1707366464)
+    np.random.seed(int(t["seed"]) if "seed" in t.files else 1707366464)
     env = environment.Environment(t["speed"], t["angle"])
     state = env.reset()
     rb = robot.Robot(env.goal_state)
@@ -68,9 +73,10 @@ def _trace_setup(environment, robot):
     return t, env, state, rb
 
 
-def test_demonstration_matches_reference(navmods):
+@pytest.mark.parametrize("name", TRACES)
+def test_demonstration_matches_reference(navmods, name):
     environment, robot = navmods
-    t, env, state, rb = _trace_setup(environment, robot)
+    t, env, state, rb = _trace_setup(environment, robot, name)
     assert np.array_equal(np.asarray(env.goal_state, np.float64), t["goal"])
     ds, da = env.get_demonstration()
     assert ds.dtype == np.float32 and ds.shape == (200, 2) and da.shape == (200, 2)
@@ -83,12 +89,19 @@ def test_demonstration_matches_reference(navmods):
     assert np.max(np.abs(ds.astype(np.float64) - ref)) <= 1e-5
 
 
-def test_robot_replays_reference_trace(navmods):
+@pytest.mark.parametrize("name", TRACES)
+def test_robot_replays_reference_trace(navmods, name):
     """robot-learning.py's loop with nav.Environment + nav.Robot, teacher-forced with the
     reference's actions (the actor weights differ): every numpy draw, reset, demonstration,
-    reward, done flag and Robot counter must follow the reference's trace."""
+    reward, done flag and Robot counter must follow the reference's trace. trace_branches.npz's
+    step actions were scripted (no get_next_action_training call, so no noise draw) to reach
+    the goal, the path's end and their coincidences with the stuck check; there the Robot's
+    goal_reached / stuck_flag are also compared right after process_transition and a goal
+    row's reward exactly."""
+    from test_oracle_branches_cpu import check_goal_row
     environment, robot = navmods
-    t, env, state, rb = _trace_setup(environment, robot)
+    t, env, state, rb = _trace_setup(environment, robot, name)
+    scripted = "step_goal" in t.files
     types = t["tick_type"]
     pushes = []
     orig = rb.memory.advance
@@ -109,11 +122,13 @@ def test_robot_replays_reference_trace(navmods):
             ds, da = env.get_demonstration()
             rb.process_demonstration(ds, da, 100.0)
         else:
-            rb.get_next_action_training(state, 100.0)  # consumes the same noise draws
+            if not scripted:
+                rb.get_next_action_training(state, 100.0)  # consumes the same noise draws
             a = t["tick_action"][i]
             ns = env.step(a)
             assert np.max(np.abs(ns - t["tick_next"][i])) < 1e-9, i
             rb.process_transition(state, a, ns, 100.0)
+            blocked = ns is state  # environment.py:125-127: the unchanged state object
             state = ns
             lo = t["push_idx"][i][0]
             slot, n = pushes[-1]
@@ -121,6 +136,11 @@ def test_robot_replays_reference_trace(navmods):
             ref_r = t["push_r"][lo]
             assert abs(row[4] - ref_r) <= 1e-4 * max(1.0, abs(ref_r)), i
             assert row[7] == float(t["push_d"][lo])
+            if scripted:
+                assert (int(rb.goal_reached), int(rb.stuck_flag)) == \
+                    (t["step_goal"][i], t["step_stuck"][i]), i
+                check_goal_row(t, i, lo, row[4])
+                assert blocked == bool(t["step_blocked"][i]), i
         cc = c[i]
         assert (rb.plan_index, rb.path_length, rb.num_episodes) == (cc[0], cc[1], cc[2]), i
         assert (int(rb.goal_reached), int(rb.stuck_flag), int(rb.demo_flag)) == \

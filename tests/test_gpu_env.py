@@ -301,11 +301,16 @@ def test_agent_step_vs_oracle_per_step(nav, orc):
     assert checked_demo > 0  # the demo term was part of the checked sums
 
 
-def test_agent_step_replays_reference_trace(nav):
-    """The reference's own headless tick loop (golden trace) replayed through nav_agent_step with
-    N = 1: same actions, same demo set, reset states injected at the reference's reset ticks."""
+def _replay_reference_trace(name, form):
+    """A reference trace through VecEnv.agent_step with N = 1 in one of the tick's launch forms:
+    "fused" (nav_agent_step_indexed), "per_env" (nav_agent_step + nav_demo_reward_indexed) or
+    "brute" (nav_agent_step + nav_demo_reward). trace_branches.npz also records goal_reached and
+    stuck_flag right after process_transition, so there every flag bit is compared as well
+    (done = push_d, goal, stuck, ended = the reference's next tick is a reset) and a goal row's
+    reward exactly (50, or 0 when stuck on the same step)."""
     from nav.vec_env import ReplayRing, VecEnv
-    t = golden("trace.npz")
+    from test_oracle_branches_cpu import check_goal_row, want_flags
+    t = golden(name)
     env = VecEnv(1, field_of(t["speed"], t["angle"]), init=False)
     types = t["tick_type"]
     first = int(np.nonzero(types == 0)[0][0])
@@ -318,7 +323,9 @@ def test_agent_step_replays_reference_trace(nav):
     env.episodes[0] = int(c[first][2])
     env.noise_scale[0] = float(c[first][6])
     env.meta[0] = 4
-    env.set_demo(t["demo_set"])
+    env.set_demo(t["demo_set"], index=form != "brute")
+    env.fuse_demo = form == "fused"
+    branches = "step_goal" in t.files
     rep = ReplayRing(2048, DEV)
     reward = torch.zeros(1, dtype=torch.float64, device=DEV)
     n_checked = 0
@@ -339,7 +346,13 @@ def test_agent_step_replays_reference_trace(nav):
         assert abs(float(rep.rows[base, 4].item()) - ref_r) <= 1e-5 * max(1.0, abs(ref_r))
         assert bool(fl & 1) == bool(t["push_d"][lo])
         assert np.max(np.abs(env.next_state[0].cpu().numpy() - t["push_s2"][lo])) < 1e-11
-        if i + 1 < len(types) and types[i + 1] == 2:
+        ended = i + 1 < len(types) and types[i + 1] == 2
+        if branches:
+            assert (fl & 15) == want_flags(t, i, lo, True if ended else None), (i, fl)
+            check_goal_row(t, i, lo, rep.rows[base, 4].item())
+            if not ended:
+                assert env.plan_index[0].item() == int(c[i][0]) + 1
+        if ended:
             assert fl & 8
             assert env.episodes[0].item() == int(c[i + 1][2])
             assert env.path_length[0].item() == int(c[i + 1][1])
@@ -349,6 +362,26 @@ def test_agent_step_replays_reference_trace(nav):
             assert not fl & 8
         n_checked += 1
     assert n_checked > 300
+
+
+@pytest.mark.parametrize("name", ["trace.npz", "trace_branches.npz", "trace_branches_field.npz"])
+def test_agent_step_replays_reference_trace(nav, name):
+    """The reference's own headless tick loop (golden trace) replayed through nav_agent_step with
+    N = 1: same actions, same demo set, reset states injected at the reference's reset ticks.
+    trace.npz is the reference's own training loop (every episode ends stuck);
+    trace_branches.npz scripts its step actions so that the goal, the path end, the stuck check
+    and their coincidences all occur, trace_branches_field.npz steers home through a
+    make_fields field (DESIGN.md has the counts)."""
+    _replay_reference_trace(name, "fused")
+
+
+@pytest.mark.parametrize("name", ["trace_branches.npz", "trace_branches_field.npz"])
+@pytest.mark.parametrize("form", ["per_env", "brute"])
+def test_agent_step_two_launch_forms_replay_branch_trace(nav, form, name):
+    """The branch trace through the tick's two-launch forms (the demo term added by
+    nav_demo_reward_indexed / nav_demo_reward after nav_agent_step): goal rows must keep their
+    exact reward there too (no demo term is added to a goal step, robot.py:744-746)."""
+    _replay_reference_trace(name, form)
 
 
 def test_demo_index_bit_exact_vs_brute_force(nav, orc):

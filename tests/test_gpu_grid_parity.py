@@ -148,6 +148,67 @@ def test_act_residual_and_noise_vs_oracle_at_bench_grid(acting, orc):
                                                          a["sc"][e], None)), e
 
 
+def test_branch_trace_at_bench_grid(nav):
+    """The indexed reward path (nav_agent_step_indexed) at the bench's grid: 65 536 envs, every
+    one replaying the reference's branch trace (trace_branches.npz: goal, path end, stuck and
+    their coincidences, NaN actions, steps clipped at a world edge). At every step tick env 0's
+    flags, next state and replay row are held to the reference's record with
+    test_agent_step_replays_reference_trace's bounds, and every other env's flags, next state,
+    counters and row equal env 0's bit for bit (one comparison on the device per tick), so a
+    workgroup or band that forms a branch differently shows."""
+    from nav.vec_env import ReplayRing, VecEnv, make_field
+    from test_oracle_branches_cpu import check_goal_row, step_ticks, want_flags
+    t = golden("trace_branches.npz")
+    n = 65536
+    env = VecEnv(n, make_field(t["speed"], t["angle"], DEV), envs_per_group=n, init=False)
+    first, ticks = step_ticks(t)
+    c = t["counters"]
+    env.state.copy_(torch.tensor(t["tick_state"][first]).expand(n, 2))
+    env.goal.copy_(torch.tensor(t["goal"]).expand(n, 2))
+    env.region.copy_(torch.tensor(t["region"]).expand(n, 4))
+    env.plan_index.fill_(int(c[first][0]))
+    env.path_length.fill_(int(c[first][1]))
+    env.episodes.fill_(int(c[first][2]))
+    env.noise_scale.fill_(float(c[first][6]))
+    env.meta.fill_(4)
+    env.set_demo(t["demo_set"])
+    assert env.fuse_demo and env.demo_index is not None
+    rep = ReplayRing(n, DEV)
+    bits = lambda x: x.view(torch.int32) if x.dtype == torch.float32 else x.view(torch.int64)  # noqa: E731
+    for i, lo, reset_state in ticks:
+        a = torch.tensor(t["tick_action"][i], device=DEV).expand(n, 2).contiguous()
+        base = env.agent_step(a, rep)
+        assert base == 0
+        same = [torch.equal(env.flags, env.flags[:1].expand(n)),
+                torch.equal(bits(env.next_state), bits(env.next_state[:1]).expand(n, 2)),
+                torch.equal(bits(rep.rows), bits(rep.rows[:1]).expand(n, 8)),
+                torch.equal(env.plan_index, env.plan_index[:1].expand(n)),
+                torch.equal(env.path_length, env.path_length[:1].expand(n)),
+                torch.equal(env.episodes, env.episodes[:1].expand(n)),
+                torch.equal(env.meta, env.meta[:1].expand(n)),
+                torch.equal(bits(env.noise_scale), bits(env.noise_scale[:1]).expand(n))]
+        assert all(same), (i, same)
+        fl = int(env.flags[0].item())
+        row = rep.rows[0].cpu().numpy()
+        ref_r = t["push_r"][lo]
+        assert (fl & 15) == want_flags(t, i, lo, reset_state), (i, fl)
+        assert abs(float(row[4]) - ref_r) <= 1e-5 * max(1.0, abs(ref_r)), i
+        check_goal_row(t, i, lo, row[4])
+        assert np.max(np.abs(env.next_state[0].cpu().numpy() - t["push_s2"][lo])) < 1e-11
+        if reset_state is not None:
+            assert env.episodes[0].item() == int(c[i + 1][2])
+            assert env.path_length[0].item() == int(c[i + 1][1])
+            # every env drew its own reset state: all of them within the region, then the
+            # reference's draw for all
+            reg = t["region"]
+            s = env.state
+            assert bool(((s[:, 0] >= reg[0]) & (s[:, 0] <= reg[1]) & (s[:, 1] >= reg[2]) &
+                         (s[:, 1] <= reg[3])).all()), i
+            env.state.copy_(torch.tensor(reset_state).expand(n, 2))
+        else:
+            assert torch.equal(bits(env.state), bits(env.state[:1]).expand(n, 2)), i
+
+
 def test_act_tick_action_equals_act_at_bench_grid(acting):
     """nav_act_tick's action_out on the same state equals nav_act's bit for bit at four
     workgroups per CU (the fused launch draws the same noise and forms the same epilogue)."""

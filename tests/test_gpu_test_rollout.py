@@ -246,6 +246,108 @@ def test_homing_episode_vs_cpu_rollout(nav, orc):
     assert np.abs(out["best_distance"].cpu().numpy() - best).max() <= 1e-9
 
 
+def test_teacher_forced_by_the_reference(nav):
+    """One launch, one env per (episode, step) pair the reference recorded in its own testing
+    loop (test_episodes.npz group a: robot-learning.py:104-117 on a make_fields field with a
+    generator-defined 2-200-200-200-2 actor): start = the reference's state at that step, goal =
+    the episode's, max_steps = 1. Every next state within 3e-4 per component of the reference's
+    (test_teacher_forced_step_parity's derived bound), reached == (distance <= 5) for EVERY pair
+    (the fixture keeps every distance 1e-3 from the threshold), best_distance within
+    3e-4 * sqrt(2) of the recorded distance. 209 pairs: three full tiles and a tail.
+    Measured maximum on an MI355X: see DESIGN.md (test episodes)."""
+    from conftest import golden
+    g = golden("test_episodes.npz")
+    n = len(g["a_ep"])
+    assert n % 64 != 0
+    env = make_env(n, g["a_speed"], g["a_angle"])
+    env.goal.copy_(torch.tensor(g["a_goal"][g["a_ep"]]))
+    actor, _ = make_actor(200, 3, int(g["a_actor_seed"]))
+    start = torch.tensor(g["a_state"], device=DEV)
+    out = {k: v.cpu().numpy() for k, v in env.test_rollout(actor, 1, start=start,
+                                                           traj=True).items()}
+    err = np.abs(out["traj"][0] - g["a_next"])
+    derr = np.abs(out["best_distance"] - g["a_dist"])
+    print(f"teacher-forced by the reference: max |next - ref| = {err.max():.3e}, "
+          f"max |best_distance - ref| = {derr.max():.3e} over {n} pairs")
+    assert err.max() <= 3e-4, int(err.max(1).argmax())
+    want = g["a_dist"] <= 5.0
+    assert 0 < want.sum() < n
+    assert np.array_equal(out["reached"].astype(bool), want)
+    assert derr.max() <= 3e-4 * np.sqrt(2.0)
+    assert (out["steps"] == 1).all()
+    assert np.array_equal(out["final_state"], out["traj"][0])
+
+
+def _reference_closed_loop(g, cap):
+    """Per episode of group (b), what the reference's testing loop gave under a cap of `cap`
+    steps: steps taken, reached, the final state, and the best distance over the steps taken.
+    For an episode that did not reach the goal that is the reference's own test_best_distance
+    (asserted here); for one that did, the reference exits before its `<` update
+    (robot-learning.py:110-114) and never reports the variable, so the minimum includes the
+    reaching step's recorded distance, as nav_test_rollout documents."""
+    from test_oracle_branches_cpu import episode_slices
+    steps, reached, final, best = [], [], [], []
+    for e, ix in enumerate(episode_slices(g, "b_")):
+        k = min(len(ix), cap)
+        hit = len(ix) <= cap
+        d = g["b_dist"][ix][:k]
+        steps.append(k)
+        reached.append(hit)
+        final.append(g["b_next"][ix][k - 1])
+        best.append(d.min())
+        ref_best = g["b_best"][e] if cap >= int(g["b_cap"]) else g["b6_best"][e]
+        if not hit:
+            assert d.min() == ref_best
+        else:
+            assert (g["b_reached_step"][e], d[-1] <= 5.0) == (k, True)
+            assert ref_best == (d[:-1].min() if k > 1 else np.inf)
+    if cap == 6:
+        assert np.array_equal(np.array(steps), g["b6_steps"])
+        assert np.array_equal(np.array(reached), g["b6_reached_step"] > 0)
+        assert np.array_equal(np.array(final), g["b6_final"])
+    return (np.array(steps, np.int32), np.array(reached), np.array(final), np.array(best))
+
+
+@pytest.mark.parametrize("form", ["single", "pop"])
+def test_closed_loop_vs_reference_episodes(nav, form):
+    """Whole test episodes against the reference's own (test_episodes.npz group b: the constant
+    field, an all-zero actor, one goal, 25 starts on a spiral, 1 to 17 steps): steps and reached
+    equal for every episode at a cap past the longest episode and at the cap of 6, final_state
+    and best_distance within 1e-9 (the device dynamics is pinned at 1e-11 per step). `pop`: the
+    same through nav_test_rollout_pop, the episodes split over 2 members holding equal actors
+    (a member holds a multiple of 64 envs: the 25 episodes repeated to fill 2 x 64)."""
+    from conftest import golden
+    from nav.mlp import DeviceMLP
+    g = golden("test_episodes.npz")
+    E = len(g["b_goal"])
+    sel = np.arange(E) if form == "single" else np.arange(128) % E
+    n = len(sel)
+    speed = np.full((100, 100), 1.0, np.float32)
+    angle = np.full((100, 100), 0.5, np.float32)
+    env = make_env(n, speed, angle)
+    env.goal.copy_(torch.tensor(g["b_goal"][sel]))
+    st = torch.tensor(g["b_start"][sel], device=DEV)
+    actors = [DeviceMLP(2, 2, 64, 2, DEV) for _ in range(2)]  # all parameters zero
+    for a in actors:
+        a.pack()
+    if form == "pop":
+        from nav.population import PopulationTable
+        pop = PopulationTable(actors, [env.p, env.p], None, n // 2)
+    seen = []
+    for cap in (int(g["b_cap"]), 6):
+        steps, reached, final, best = _reference_closed_loop(g, cap)
+        assert steps.max() <= cap
+        out = env.test_rollout(actors[0], cap, start=st) if form == "single" else \
+            env.test_rollout_pop(pop, cap, start=st)
+        out = {k: v.cpu().numpy() for k, v in out.items()}
+        assert np.array_equal(out["steps"], steps[sel])
+        assert np.array_equal(out["reached"].astype(bool), reached[sel])
+        assert np.abs(out["final_state"] - final[sel]).max() <= 1e-9
+        assert np.abs(out["best_distance"] - best[sel]).max() <= 1e-9
+        seen.append((int(reached.sum()), int((~reached).sum())))
+    assert seen[0] == (E, 0) and min(seen[1]) >= 5  # all reach; the cap of 6 cuts 12 off
+
+
 def test_start_draw(nav, orc):
     """start = NULL: env e starts at region_sample(region[e], u01(w.x, w.y), u01(w.z, w.w)), w =
     philox(0, e, NAV_TAG_TEST = 6, episode): the first step equals the explicit-start run from the
