@@ -5,25 +5,18 @@ split counts recorded from the library before the learner sources were split int
 reduce_adam.h, learner_host.h, learner_kernels.hip and learner_pop.hip. The population entry
 points' table is tests/test_population_learner_cpu.py."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-from conftest import PKG
+from abi_args import EINVAL, F, Call, load_raw
+from abi_args import v as _v
 
-LIB = os.path.join(PKG, "nav", "libnavenv.so")
-EINVAL = -100000
-F = 16  # a non-null pointer value that is never dereferenced on the host
 NAN = float("nan")
 
 
 @pytest.fixture(scope="module")
 def raw():
-    if not os.path.exists(LIB):
-        subprocess.run(["make", "-s", "-j4", "-C", PKG], check=True)
-    from nav import _lib
-    return _lib.lib().raw
+    return load_raw()
 
 
 def net(d_in=4, d_out=1, hidden=64, n_hidden=2):
@@ -42,22 +35,6 @@ def ptrs(*v):
 
 def floats(*v):
     return (C.c_float * len(v))(*v)
-
-
-class Call:
-    """A valid argument set of one entry point, by name; a case alters some of them."""
-
-    def __init__(self, fn, **valid):
-        self.fn, self.valid = fn, valid
-
-    def __call__(self, lib, **changed):
-        assert set(changed) <= set(self.valid), changed
-        args = {k: (changed[k] if k in changed else v)() for k, v in self.valid.items()}
-        return getattr(lib, self.fn)(*args.values())
-
-
-def _v(x):
-    return lambda: x
 
 
 TWINS = lambda: nets(net(), net())  # noqa: E731

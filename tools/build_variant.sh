@@ -2,7 +2,7 @@
 # Build an A/B variant of libnavenv.so with extra -D flags on some translation units (tuning
 # only), through the package Makefile's UNIT hook: one flag list, one object list.
 #   tools/build_variant.sh NAME "UNIT ..." "-DFOO=1 ..."
-#   UNIT: learner | env | mlpN (the row kernels of hidden width 32*N; mlp8 = 256) | mlp0 (the row
+#   UNIT: learner | env | demo_reward | demo_index | demonstrator | mlpN (the row kernels of hidden width 32*N; mlp8 = 256) | mlp0 (the row
 #   kernels' C-ABI object; "mlp0 mlp8" rebuilds the dispatch and the 256-wide kernels together) |
 #   mlp8agpr (mlp8 without the scheduler / VGPR-form flags); NOSCHED=1 in the environment drops
 #   those flags from every unit named
@@ -17,6 +17,7 @@ for u in $2; do
   case $u in
     learner) units="$units learner_kernels" ;;
     env) units="$units env_kernels" ;;
+    demo_reward|demo_index|demonstrator) units="$units $u" ;;
     mlp0) units="$units mlp_abi" ;;
     mlp[1-8]) units="$units mlp_nt${u#mlp}" ;;
     mlp8agpr) units="$units mlp_nt8"; plain=1 ;;
