@@ -218,7 +218,15 @@ int nav_demo_index_subfill(const double* demo_xy, const int64_t* demo_off, int32
                            const double* sub_bound, const int64_t* sub_start, int32_t* sub_cand,
                            void* stream);
 /* nav_demo_reward through the level-2 index (same result, a few instead of 11 355 points per
- * env; block_stats as there). */
+ * env; block_stats as there).
+ * Contract of the indexed entry points (this one, nav_agent_step_indexed, nav_act_tick(_pop)): a
+ * state outside the index, i.e. outside [0,100)^2, is answered by brute force over the group's
+ * demo_xy[demo_off[g] .. demo_off[g+1]). With demo_off == NULL these entry points carry no m, so
+ * that fallback has no point to visit: they then REQUIRE every flagged s' inside [0,100)^2 (the
+ * ticks' own next states always are: the dynamics clip to [0, 98.9999]). A caller who cannot
+ * guarantee that, such as one handing its own next_state to nav_demo_reward_indexed, passes a
+ * shared set as one group: a two-entry demo_off = {0, m} with envs_per_group >= n, and the index
+ * built from the same table (its lists equal the demo_off == NULL build's entry for entry). */
 int nav_demo_reward_indexed(const nav_params* p, int64_t n, const double* next_state,
                             const double* goal_term, const uint8_t* flags, const double* demo_xy,
                             const int64_t* demo_off, int32_t envs_per_group,

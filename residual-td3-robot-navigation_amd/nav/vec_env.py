@@ -143,6 +143,7 @@ class VecEnv:
         self.demo_xy = None
         self.demo_off = None
         self.demo_index = None
+        self._shared_off = None  # a shared set's {0, m} offset table (set_demo)
         # demo reward fused into the tick launch (nav_agent_step_indexed); False keeps the two
         # launches (A/B and the fused-vs-unfused parity test)
         self.fuse_demo = bool(fuse_demo)
@@ -189,9 +190,22 @@ class VecEnv:
         self.demo_xy = torch.as_tensor(demo_xy, dtype=torch.float64).reshape(-1, 2).contiguous()
         self.demo_xy = self.demo_xy.to(self.device)
         self.demo_off = None
+        self._shared_off = None
         if demo_off is not None:
             self.demo_off = torch.as_tensor(demo_off, dtype=torch.int64).to(self.device)
-        self.demo_index = DemoIndex(self.demo_xy, self.demo_off) if index else None
+        elif self.demo_xy.shape[0] > 0:
+            # A shared set goes to the indexed entry points as one group of all envs: with
+            # demo_off == NULL they carry no m, so a next state outside [0,100)^2 would find no
+            # point to fall back to (navenv.h). The lists are the shared form's, entry for entry.
+            self._shared_off = torch.tensor([0, self.demo_xy.shape[0]], dtype=torch.int64,
+                                            device=self.device)
+        self.demo_index = DemoIndex(self.demo_xy, self._index_groups()[0]) if index else None
+
+    def _index_groups(self):
+        """(demo_off, envs_per_group) as the indexed entry points take them"""
+        if self.demo_off is None and self._shared_off is not None:
+            return self._shared_off, max(self.n, 1)
+        return self.demo_off, self.envs_per_group
 
     # one fused training tick (robot.py:443-506, 645-675 + environment.py:122-137)
     def agent_step(self, action, replay, stream=None, reward_out=None):
@@ -201,11 +215,12 @@ class VecEnv:
         ix = self.demo_index if (self.demo_xy is not None and self.demo_xy.shape[0] > 0) else None
         if ix is not None and self.fuse_demo:
             # one launch: tick + indexed demo reward (bit-identical to the two-launch path)
+            off, epg = self._index_groups()
             with prof.region("agent_step", float(prof.AGENT_STEP_BYTES * self.n)):
                 lib().nav_agent_step_indexed(
                     C.byref(self.p), C.byref(self.soa), ptr(self.field), ptr(action), C.byref(rd),
-                    base, C.byref(self.out), ptr(self.demo_xy), ptr(self.demo_off),
-                    self.envs_per_group, ptr(ix.cell_start), ptr(ix.cand), ptr(reward_out), s)
+                    base, C.byref(self.out), ptr(self.demo_xy), ptr(off), epg,
+                    ptr(ix.cell_start), ptr(ix.cand), ptr(reward_out), s)
             replay.advance(self.n)
             return base
         has_demo = self.demo_xy is not None and self.demo_xy.shape[0] > 0
@@ -214,27 +229,33 @@ class VecEnv:
                                  ptr(action), C.byref(rd), base, C.byref(self.out),
                                  int(has_demo), s)
         if has_demo:
+            self.demo_reward(replay, base, reward_out=reward_out, stream=stream)
+        replay.advance(self.n)
+        return base
+
+    # the two-launch tick's second launch: the demo-proximity term (robot.py:749-757) of the envs
+    # the tick flagged, from next_state / goal_term / flags as they stand, into the rows at `base`
+    def demo_reward(self, replay, base, reward_out=None, stream=None):
+        s = stream_handle(stream)
+        rd = replay.desc()
+        ix = self.demo_index
+        if ix is not None:
+            off, epg = self._index_groups()
+            # algorithmic work: the f64 ops over the candidates actually visited
+            with prof.region("demo_reward", prof.demo_flops(self.n, ix.mean_candidates)):
+                lib().nav_demo_reward_indexed(
+                    C.byref(self.p), self.n, ptr(self.next_state), ptr(self.goal_term),
+                    ptr(self.flags), ptr(self.demo_xy), ptr(off), epg, ptr(ix.cell_start),
+                    ptr(ix.cand), C.byref(rd), base, ptr(reward_out), ptr(self.block_stats), s)
+        else:
             m = self.demo_xy.shape[0] if self.demo_off is None else 0
             m_per = self.demo_xy.shape[0] if self.demo_off is None else \
                 self.demo_xy.shape[0] / max(1, self.demo_off.shape[0] - 1)
-            ix = self.demo_index
-            if ix is not None:
-                # algorithmic work: the f64 ops over the candidates actually visited
-                with prof.region("demo_reward", prof.demo_flops(self.n, ix.mean_candidates)):
-                    lib().nav_demo_reward_indexed(
-                        C.byref(self.p), self.n, ptr(self.next_state), ptr(self.goal_term),
-                        ptr(self.flags), ptr(self.demo_xy), ptr(self.demo_off),
-                        self.envs_per_group, ptr(ix.cell_start), ptr(ix.cand), C.byref(rd), base,
-                        ptr(reward_out), ptr(self.block_stats), s)
-            else:
-                with prof.region("demo_reward", prof.demo_flops(self.n, m_per)):
-                    lib().nav_demo_reward(C.byref(self.p), self.n, ptr(self.next_state),
-                                          ptr(self.goal_term), ptr(self.flags),
-                                          ptr(self.demo_xy), ptr(self.demo_off), m,
-                                          self.envs_per_group, C.byref(rd), base,
-                                          ptr(reward_out), ptr(self.block_stats), s)
-        replay.advance(self.n)
-        return base
+            with prof.region("demo_reward", prof.demo_flops(self.n, m_per)):
+                lib().nav_demo_reward(C.byref(self.p), self.n, ptr(self.next_state),
+                                      ptr(self.goal_term), ptr(self.flags), ptr(self.demo_xy),
+                                      ptr(self.demo_off), m, self.envs_per_group, C.byref(rd),
+                                      base, ptr(reward_out), ptr(self.block_stats), s)
 
     # robot.py:541-569 + the training tick above, one launch (nav_act_tick): the actor's action
     # epilogue runs each env's tick in the same workgroup
@@ -247,12 +268,13 @@ class VecEnv:
         if self.demo_xy is not None and self.demo_xy.shape[0] > 0 and ix is None:
             raise ValueError("act_tick needs the demo index (set_demo(index=True))")
         flops = prof.mlp_fwd_flops(2, 2, actor.hidden, actor.n_hidden, self.n)
+        off, epg = self._index_groups()
         with prof.region("act_tick", flops):
             lib().nav_act_tick(
                 C.byref(self.p), C.byref(a), C.byref(self.soa), ptr(self.field), ptr(noise_z),
                 int(step) & 0xFFFFFFFF, 0 if training else 1, C.byref(rd), base,
                 C.byref(self.out), ptr(self.demo_xy) if ix else None,
-                ptr(self.demo_off) if ix else None, self.envs_per_group,
+                ptr(off) if ix else None, epg,
                 ptr(ix.cell_start) if ix else None, ptr(ix.cand) if ix else None,
                 ptr(action_out), ptr(reward_out), stream_handle(stream))
         replay.advance(self.n)
