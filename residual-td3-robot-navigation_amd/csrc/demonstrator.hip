@@ -213,10 +213,14 @@ __global__ __launch_bounds__(kBlock) void k_demo_augment(int32_t n_demo, int32_t
     out[idx] = v;
 }
 
-// environment.py:166-171: the E best paths (np.argsort ascending, last E; ties by path index, a
-// stable order), their float32 action mean and std over the elites in that order (numpy's float32
-// reductions: sequential sums, / E, sqrt); best [n] = argmax of the rewards (first maximum,
-// environment.py:173). Workgroup = problem; P <= kBlock.
+// environment.py:166-171: the E best paths (np.argsort ascending, last E), their float32 action
+// mean and std over the elites in that order (numpy's float32 reductions: sequential sums, / E,
+// sqrt); best [n] = argmax of the rewards (first maximum, environment.py:173). Tied rewards follow
+// ascending reward, then path index: numpy's default argsort promises no order for exact ties, so
+// this rule is the project's definition there. It decides elite membership and the float32
+// summation order, and is pinned by tests/test_gpu_cem_kernels.py (planted ties, a fully tied
+// plan) against tests/cem_ref.py, itself held to np.argsort(kind="stable") and the golden
+// demonstrations by tests/test_cem_ref_cpu.py. Workgroup = problem; P <= kBlock.
 __global__ __launch_bounds__(kBlock) void k_cem_elite(int32_t P, int32_t T, int32_t E,
                                                       const double* __restrict__ reward,
                                                       const float* __restrict__ actions,

@@ -7,8 +7,15 @@ nav_cem_rollout launch per iteration over every problem's paths, then one nav_ce
 on the host from each group's own RandomState in the order robot-learning.py's demo ticks make
 them (start state, CEM actions, then the demonstration's augmentation noise, demo after demo), so
 each plan equals nav.Environment.get_demonstration's on the same stream (tests/test_gpu_cem.py).
-Elite order: ascending reward, ties by path index; np.argsort orders exact ties
-platform-dependently (x86-simd-sort), so plans with tied elite rewards are the one case not pinned.
+Elite order: ascending reward, then path index (a stable order). numpy's default argsort does not
+promise an order for exact ties (x86-simd-sort orders them platform-dependently), so for tied
+rewards this rule is the project's definition. Ties do occur (paths clamped into a corner of the
+world, float32 rounding of the final state: tests/test_cem_ref_cpu.py finds them in the golden
+traces), and the rule is pinned: tests/cem_ref.py restates the planner in numpy,
+tests/test_cem_ref_cpu.py holds that restatement to the reference's golden demonstrations and to
+np.argsort(kind="stable"), and tests/test_gpu_cem_kernels.py holds nav_cem_elite to it with ties
+planted among the elites, on the elite cutoff, across it and at the maximum, and a whole plan to it
+whose rewards are all tied in every iteration.
 """
 import ctypes as C
 

@@ -1,7 +1,8 @@
 """Batched CEM demonstrator (environment.py:140-179) vs the N = 1 drop-in's get_demonstration on
 the same numpy stream (that one is pinned to the reference's own outputs by
 tests/test_gpu_dropin.py): every group's 3 demonstrations, bit for bit, and the group demo sets
-built from them."""
+built from them; and against the CPU restatement tests/cem_ref.py. The kernels one by one, at other
+shapes and with tied rewards: tests/test_gpu_cem_kernels.py."""
 import numpy as np
 import pytest
 import torch
@@ -22,7 +23,9 @@ def _groups(G, seed):
 
 
 def test_batched_cem_equals_dropin_demonstrations():
+    import cem_ref
     from nav import _lib
+    from nav import config as K
     from nav.cem import batched_demonstrations, group_stream_draws
     from nav.demos import augment, demo_set_from
     from nav.environment import Environment
@@ -40,6 +43,18 @@ def test_batched_cem_equals_dropin_demonstrations():
     st, ac = batched_demonstrations(field, np.repeat(regions, nd, 0), np.repeat(goals, nd, 0), uni,
                                     a0, z, DEV)
     st, ac = st.cpu().numpy(), ac.cpu().numpy()
+    # the workload's shape against the CPU restatement (tests/cem_ref.py, pinned to the golden
+    # demonstrations by tests/test_cem_ref_cpu.py): actions bit for bit, states within one float32
+    # ulp, given that no reward pair that decides an elite set or best is nearer than 1e-4
+    ref = cem_ref.demonstrations(speed, angle, np.repeat(regions, nd, 0), np.repeat(goals, nd, 0),
+                                 uni, a0, z, K.DEMOS_CEM_NUM_ELITES)
+    assert ref["actions"].shape[:4] == (K.DEMOS_CEM_NUM_ITERATIONS, G * nd, K.DEMOS_CEM_NUM_PATHS,
+                                        K.DEMOS_CEM_PATH_LENGTH)
+    cem_ref.assert_decisive_gaps(ref["reward"], K.DEMOS_CEM_NUM_ELITES)
+    for k in range(G * nd):
+        assert np.array_equal(ac[k], ref["plan_actions"][k]), k
+        ulp = np.abs(st[k].view(np.int32).astype(np.int64) - ref["states"][k].view(np.int32))
+        assert ulp.max() <= 1, (k, int(ulp.max()))
     env = Environment(speed, angle)
     for g in range(G):
         # the drop-in on the group's stream: demo, its augmentation draws, next demo ...
