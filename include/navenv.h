@@ -689,6 +689,47 @@ int nav_grad_reduce_adam_pop(const nav_td3_member* members, int32_t n_members, i
                              float eps, double bc1, float bc2_sqrt, int32_t soft_update,
                              void* stream);
 
+/* ---- Population learner with demonstrations: per-member demo mix and BC term ----
+ * Beside members[m], what member m's nav_td3_mix_idx and nav_td3_actor_rows_bc calls take: the
+ * demonstration prefix of its batches, the rows in the tail behind its ring (at the common ring
+ * capacity) and the two weights of the actor's loss. A host array [n_members]. */
+typedef struct nav_td3_member_bc {
+    int64_t B_demo;        /* rows b < B_demo of both batches are demonstration rows; 0 .. B */
+    int64_t n_demo;        /* rows in the tail behind this member's ring */
+    float q_weight, bc_weight;
+    int64_t* idx_critic;   /* [B], written by the mix launch; must equal members[m].idx_critic */
+    int64_t* idx_actor;    /* [B]; must equal members[m].idx_actor */
+    float* bc_part;        /* [nav_mlp_row_blocks(B)] */
+} nav_td3_member_bc;
+/* `bc_table` is device memory of nav_td3_pop_bc_table_bytes(n_members) bytes (n_members times
+ * the size for one) that nav_td3_pop_bc_table_build fills on the stream with what the two
+ * launches below read: member m's nav_td3_actor_rows_bc arguments (the critic's dy seed
+ * (float)(-q_weight/B) and the BC coefficient B_demo ? (float)(2*bc_weight/B_demo) : 0, formed as
+ * that entry point forms them) and its mix description. Built as nav_td3_pop_table_build's table:
+ * once per population, and again only when a pointer or a hyper-parameter changes; `size` and
+ * `counter` travel by value. The table nav_td3_pop_table_build fills is neither read nor changed.
+ * Host checks of all three entry points (NAV_EINVAL, before any HIP call): everything
+ * nav_td3_actor_rows_pop checks; bc or bc_table NULL; B_demo < 0 or > B; bc_weight != 0 with
+ * B_demo == 0; B_demo > 0 with n_demo < 1; bc_part NULL; an idx_* pointer NULL or different from
+ * members[m]'s. */
+int64_t nav_td3_pop_bc_table_bytes(int32_t n_members);
+int nav_td3_pop_bc_table_build(const nav_td3_member* members, const nav_td3_member_bc* bc,
+                               int32_t n_members, int64_t B, void* bc_table, void* stream);
+/* nav_td3_mix_idx of every member in one launch (grid.y = the member): member m writes its
+ * idx_critic and, with actor_too != 0, its idx_actor, from its own seed, B_demo and n_demo with
+ * demo_base = the common ring capacity; each array equals member m's own nav_td3_mix_idx call with
+ * the same size and counter bit for bit. */
+int nav_td3_mix_idx_pop(const nav_td3_member* members, const nav_td3_member_bc* bc,
+                        int32_t n_members, int64_t B, const void* bc_table, int64_t size,
+                        uint32_t counter, int32_t actor_too, void* stream);
+/* nav_td3_actor_rows_bc (with a critic) of every member in one launch: grid (row blocks, 1,
+ * members), no L2 warmer rows. Every output of member m equals its own nav_td3_actor_rows_bc with
+ * the same size and counter bit for bit, so a member with B_demo = 0, bc_weight = 0 and
+ * q_weight = 1 equals nav_td3_actor_rows_pop's output for it. */
+int nav_td3_actor_rows_bc_pop(const nav_td3_member* members, const nav_td3_member_bc* bc,
+                              int32_t n_members, int64_t B, const void* bc_table, int64_t size,
+                              uint32_t counter, void* stream);
+
 /* ---- Population-based training: clone learners inside a population in ONE launch ----
  * For every pair j, member dst[j] receives a byte-for-byte copy of member src[j]'s learner state:
  * `params` of the six networks (actor, critics[2], target_actor, target_critics[2]), their

@@ -2,7 +2,8 @@
 // learner_kernels.hip with one more grid dimension, the member (blockIdx.y). A workgroup reads its
 // member's argument struct from the device table through a block-uniform pointer and runs the
 // same body (wgrad.h, reduce_adam.h) on it. An object of its own (learner_pop.o), so the plain
-// kernels' object holds what it held before.
+// kernels' object holds what it held before. Also the population's demonstration mix
+// (k_td3_mix_idx_pop), launched for mlp_abi.hip's nav_td3_mix_idx_pop.
 #include "learner_host.h"
 
 namespace {
@@ -43,6 +44,29 @@ __global__ __launch_bounds__(kBlock) void k_pack_img_pop(const LearnMember* __re
                                                          int set) {
     const PackArgs& a = tab[blockIdx.y].pack[set];
 #include "pack_img_body.inc"
+}
+
+// k_td3_mix_idx (learner_kernels.hip) with the member on grid.y: member m's seed, B_demo, n_demo
+// and index arrays from its MixMember, the same Philox draws and the same two formulas
+struct MixPopArgs {
+    const MixMember* tab;
+    int64_t size, B, demo_base;
+    uint32_t ctr0;
+    int32_t actor_too;
+};
+__global__ __launch_bounds__(kBlock) void k_td3_mix_idx_pop(MixPopArgs a) {
+    const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (b >= a.B) return;
+    const MixMember& m = a.tab[blockIdx.y];
+    const bool demo = b < m.B_demo;
+#pragma unroll
+    for (int y = 0; y < 2; ++y) {
+        if (y == 1 && !a.actor_too) continue;
+        const uint4 w = philox((uint32_t)b, 0u, demo ? NAV_TAG_DEMO : NAV_TAG_SAMPLE,
+                               a.ctr0 + (uint32_t)y, m.s0, m.s1);
+        m.out[y][b] = demo ? a.demo_base + (int64_t)(((uint64_t)w.x * (uint64_t)m.n_demo) >> 32)
+                           : (int64_t)(((uint64_t)w.x * (uint64_t)a.size) >> 32);
+    }
 }
 
 // One member's entry (every check of the single-member entry points on the way); blocks[w]: grid.x
@@ -130,6 +154,17 @@ int navi_learner_pop_fill(const nav_td3_member* members, int32_t n_members, int6
     int blocks[3];
     return learn_pop_check(members, n_members, B, splits_critic, splits_actor,
                            static_cast<LearnMember*>(dst), e0, blocks);
+}
+
+int navi_mix_idx_pop_launch(const void* mix, int32_t n_members, int64_t B, int64_t size,
+                            int64_t demo_base, uint32_t counter, int32_t actor_too,
+                            hipStream_t st) {
+    MixPopArgs a{static_cast<const MixMember*>(mix), size, B, demo_base, 2u * counter,
+                 actor_too ? 1 : 0};
+    hipLaunchKernelGGL(k_td3_mix_idx_pop, dim3((unsigned)blocks_for(B), (unsigned)n_members),
+                       dim3(kBlock), 0, st, a);
+    NAV_CHECK_LAUNCH();
+    return 0;
 }
 
 extern "C" {

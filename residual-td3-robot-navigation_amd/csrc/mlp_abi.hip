@@ -4,7 +4,7 @@
 #include "mlp_rows_role.h"
 #include "pop_host.h"
 
-// the 4 x 8 launcher objects' dispatchers
+// the 5 x 8 launcher objects' dispatchers
 #define NAV_ROWS_DECL(role, nt) rows_fn NAV_ROWS_FN(role, nt);
 #define NAV_ROWS_DECL_ROLE(role) NAV_ROWS_NTS(NAV_ROWS_DECL, role)
 NAV_ROWS_ROLES(NAV_ROWS_DECL_ROLE)
@@ -257,6 +257,42 @@ int td3_pop_check(const nav_td3_member* members, int32_t n_members, int64_t B,
         if (act) act[m] = a;
     }
     return 0;
+}
+
+// ---- the population's BC table, mix launch and BC actor launch ----
+// The host-side check the three entry points share (before any HIP call): td3_pop_check, then per
+// member what nav_td3_actor_rows_bc and nav_td3_mix_idx refuse and the index pointers the two
+// arrays must agree on. rows / mix (nullable): [n_members] host entries of the table's sections,
+// the BC arguments formed exactly as nav_td3_actor_rows_bc forms them.
+int td3_pop_bc_check(const nav_td3_member* members, const nav_td3_member_bc* bc,
+                     int32_t n_members, int64_t B, const void* table, ActorRowsBcArgs* rows,
+                     MixMember* mix) {
+    if (!bc || !table || !members_same_shape(members, n_members) || B < 1) return NAV_EINVAL;
+    for (int m = 0; m < n_members; ++m) {
+        const nav_td3_member& t = members[m];
+        const nav_td3_member_bc& x = bc[m];
+        if (x.B_demo < 0 || x.B_demo > B || (x.bc_weight != 0.f && x.B_demo == 0) ||
+            (x.B_demo > 0 && (x.n_demo < 1 || x.n_demo > ((int64_t)1 << 32))) || !x.bc_part ||
+            !x.idx_critic || !x.idx_actor || x.idx_critic != t.idx_critic ||
+            x.idx_actor != t.idx_actor)
+            return NAV_EINVAL;
+        CriticRowsArgs c{};
+        ActorRowsBcArgs e{};
+        const int rc = rows_member_fill(t, B, c, e.r);
+        if (rc) return rc;
+        e.r.dq = (float)(-(double)x.q_weight / (double)B);
+        e.bc.B_demo = x.B_demo;
+        e.bc.bc_coef = x.B_demo > 0 ? (float)(2.0 * (double)x.bc_weight / (double)x.B_demo) : 0.f;
+        e.bc.bc_part = x.bc_part;
+        if (rows) rows[m] = e;
+        if (mix) mix[m] = MixMember{x.B_demo, x.n_demo, t.seed_lo, t.seed_hi,
+                                    {x.idx_critic, x.idx_actor}};
+    }
+    return 0;
+}
+
+bool pop_size_ok(const nav_td3_member* members, int64_t size) {
+    return size >= 1 && size <= members[0].replay.capacity && size <= ((int64_t)1 << 32);
 }
 
 }  // namespace
@@ -656,6 +692,55 @@ int nav_td3_critic_rows_pop(const nav_td3_member* members, int32_t n_members, in
 int nav_td3_actor_rows_pop(const nav_td3_member* members, int32_t n_members, int64_t B,
                            const void* table, int64_t size, uint32_t counter, void* stream) {
     return rows_pop_launch(members, n_members, B, table, size, counter, 0, FAM_ACTOR_POP, stream);
+}
+
+int64_t nav_td3_pop_bc_table_bytes(int32_t n_members) {
+    static_assert(sizeof(ActorRowsBcArgs) % 8 == 0, "the table's sections stay 8-byte aligned");
+    if (n_members < 1 || n_members > kMaxMembers) return NAV_EINVAL;
+    return (int64_t)n_members * (int64_t)(sizeof(ActorRowsBcArgs) + sizeof(MixMember));
+}
+
+int nav_td3_pop_bc_table_build(const nav_td3_member* members, const nav_td3_member_bc* bc,
+                               int32_t n_members, int64_t B, void* bc_table, void* stream) {
+    if (!bc_table || n_members < 1 || n_members > kMaxMembers) return NAV_EINVAL;
+    const int64_t bytes = nav_td3_pop_bc_table_bytes(n_members);
+    // the host image: [P] ActorRowsBcArgs | [P] MixMember
+    uint32_t* host = static_cast<uint32_t*>(calloc((size_t)bytes / 4 + 1, 4));
+    if (!host) return NAV_EINVAL;
+    char* h = reinterpret_cast<char*>(host);
+    int rc = td3_pop_bc_check(
+        members, bc, n_members, B, bc_table, reinterpret_cast<ActorRowsBcArgs*>(h),
+        reinterpret_cast<MixMember*>(h + (size_t)n_members * sizeof(ActorRowsBcArgs)));
+    if (!rc) rc = navi_table_write(host, bytes, bc_table, S(stream));
+    free(host);
+    return rc;
+}
+
+int nav_td3_mix_idx_pop(const nav_td3_member* members, const nav_td3_member_bc* bc,
+                        int32_t n_members, int64_t B, const void* bc_table, int64_t size,
+                        uint32_t counter, int32_t actor_too, void* stream) {
+    const int rc = td3_pop_bc_check(members, bc, n_members, B, bc_table, nullptr, nullptr);
+    if (rc) return rc;
+    if (!pop_size_ok(members, size)) return NAV_EINVAL;
+    return navi_mix_idx_pop_launch(
+        static_cast<const char*>(bc_table) + (size_t)n_members * sizeof(ActorRowsBcArgs),
+        n_members, B, size, members[0].replay.capacity, counter, actor_too, S(stream));
+}
+
+int nav_td3_actor_rows_bc_pop(const nav_td3_member* members, const nav_td3_member_bc* bc,
+                              int32_t n_members, int64_t B, const void* bc_table, int64_t size,
+                              uint32_t counter, void* stream) {
+    const int rc = td3_pop_bc_check(members, bc, n_members, B, bc_table, nullptr, nullptr);
+    if (rc) return rc;
+    if (!pop_size_ok(members, size)) return NAV_EINVAL;
+    RowsPopLaunch a{};
+    a.k.table = bc_table;
+    a.k.size = size;
+    a.k.counter = counter;
+    a.B = B;
+    a.n_hidden = members[0].critics[0].n_hidden;
+    a.n_members = n_members;
+    return rows_dispatch(members[0].actor.hidden_pad, FAM_ACTOR_BC_POP, 0, 0, &a, 1, B, S(stream));
 }
 
 int64_t nav_mlp_mask_count(int32_t hidden_pad, int32_t n_hidden, int64_t M) {

@@ -1984,9 +1984,22 @@ __global__ __launch_bounds__(kBlock, 1) void k_td3_actor_rows_bc(ActorRowsBcArgs
     const ActorBcExtra& bx = x.bc;
 #include "td3_actor_rows_body.inc"
 }
+// the population's BC form (nav_td3_actor_rows_bc_pop): grid.z is the member, whose
+// ActorRowsBcArgs the workgroup reads from the BC table (nav_td3_pop_bc_table_build) through a
+// block-uniform pointer; size and counter from `pv` as in k_td3_actor_rows_pop
+template <int NT, int RT, int CBM>
+__global__ __launch_bounds__(kBlock, 1) void k_td3_actor_rows_bc_pop(RowsPop pv) {
+    constexpr bool POP = true;
+    constexpr int MODE = ACTOR_TD3_BC;
+    const ActorRowsBcArgs& x = static_cast<const ActorRowsBcArgs*>(pv.table)[blockIdx.z];
+    const ActorRowsArgs& a = x.r;
+    const ActorBcExtra& bx = x.bc;
+#include "td3_actor_rows_body.inc"
+}
 
 // what a population launch passes to the per-NT objects (the table's row sections are
-// [n_members] CriticRowsArgs, then [n_members] ActorRowsArgs)
+// [n_members] CriticRowsArgs, then [n_members] ActorRowsArgs; the BC table's is [n_members]
+// ActorRowsBcArgs)
 struct RowsPopLaunch {
     RowsPop k;
     int64_t B;
@@ -2011,7 +2024,7 @@ int row_tiles_for(int64_t M, bool tick) { return (!tick && M <= kSmallRows) ? 1 
 // them through nav_mlp_rows_<role>_<NT>(). Argument structs travel as const void* (same definitions).
 enum {
     FAM_FWD = 0, FAM_BWD = 1, FAM_CRITIC = 2, FAM_ACTOR = 3, FAM_TEST = 4, FAM_TEST_POP = 5,
-    FAM_CRITIC_POP = 6, FAM_ACTOR_POP = 7, FAM_ACTOR_BC = 8
+    FAM_CRITIC_POP = 6, FAM_ACTOR_POP = 7, FAM_ACTOR_BC = 8, FAM_ACTOR_BC_POP = 9
 };
 
 }  // namespace

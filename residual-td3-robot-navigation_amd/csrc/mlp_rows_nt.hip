@@ -1,5 +1,5 @@
 // mlp_rows_nt.hip — the launchers of the row kernels (mlp_rows.h) of one hidden width, hp = 32 *
-// NAV_MLP_PART, and one role (NAV_MLP_ROLE, mlp_rows_role.h): 8 x 4 independent objects, so make
+// NAV_MLP_PART, and one role (NAV_MLP_ROLE, mlp_rows_role.h): 8 x 5 independent objects, so make
 // -j compiles the heavy template instantiations in parallel. Each exports one dispatcher,
 // nav_mlp_rows_<role>_<NT>(), that mlp_abi.hip calls; the role decides which kernels the object
 // instantiates.
@@ -110,6 +110,15 @@ void launch_actor_rows_pop(const RowsPopLaunch& a, hipStream_t st) {
              st, a.k);
 }
 
+// the population's BC form: the BC kernel's LDS, the population forms' grid
+template <int NT, int RT>
+void launch_actor_rows_bc_pop(const RowsPopLaunch& a, hipStream_t st) {
+    constexpr int TM = RT * 32;
+    auto k = a.n_hidden == 1 ? k_td3_actor_rows_bc_pop<NT, RT, 0> : k_td3_actor_rows_bc_pop<NT, RT, 1>;
+    launch_k(k, dim3(row_blocks(a.B, TM), 1u, (unsigned)a.n_members),
+             actor_rows_bc_lds(TM, NT * 32), st, a.k);
+}
+
 template <int NT, int RT, bool POP>
 void launch_test(const TestArgs& a, hipStream_t st) {
     constexpr int TM = RT * 32;
@@ -124,6 +133,8 @@ int rows_rt(int fam, int in_mode, int out_mode, const void* args, int n_nets, hi
     if (rows_role(fam, out_mode) != ROLE) return NAV_EINVAL;
     if constexpr (ROLE == ROLE_BC) {
         launch_actor_rows_bc<NT, RT>(*static_cast<const ActorRowsBcArgs*>(args), st);
+    } else if constexpr (ROLE == ROLE_BCPOP) {
+        launch_actor_rows_bc_pop<NT, RT>(*static_cast<const RowsPopLaunch*>(args), st);
     } else if constexpr (ROLE == ROLE_LPOP) {
         const RowsPopLaunch& a = *static_cast<const RowsPopLaunch*>(args);
         if (fam == FAM_CRITIC_POP)

@@ -9,9 +9,25 @@
 // (pop_state.hip). 0 or the negated HIP error.
 int navi_table_write(const void* host, int64_t bytes, void* dev, hipStream_t st);
 
+// nav_td3_mix_idx_pop's launch (learner_pop.hip) after mlp_abi.hip's checks: `mix` is the BC
+// table's [n_members] MixMember section
+int navi_mix_idx_pop_launch(const void* mix, int32_t n_members, int64_t B, int64_t size,
+                            int64_t demo_base, uint32_t counter, int32_t actor_too,
+                            hipStream_t st);
+
 namespace nav {
 
 constexpr int kMaxMembers = 256;
+
+// One member's entry of the BC table's second section (nav_td3_pop_bc_table_build writes it in
+// mlp_abi.hip, k_td3_mix_idx_pop reads it in learner_pop.hip): what nav_td3_mix_idx takes per
+// member; the fill, the counter, B and the common capacity travel with the launch.
+struct MixMember {
+    int64_t B_demo, n_demo;
+    uint32_t s0, s1;
+    int64_t* out[2];  // idx_critic, idx_actor
+};
+static_assert(sizeof(MixMember) % 8 == 0, "the table's sections stay 8-byte aligned");
 
 inline bool same_net_shape(const nav_mlp& a, const nav_mlp& b) {
     return a.d_in == b.d_in && a.d_out == b.d_out && a.hidden == b.hidden &&

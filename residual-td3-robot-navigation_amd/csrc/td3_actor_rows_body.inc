@@ -2,7 +2,8 @@
 // td3_critic_rows_body.inc). MODE (constexpr, ACTOR_PLAIN in the plain and population kernels)
 // selects the behaviour-cloning forms of k_td3_actor_rows_bc, whose extras arrive in `bx`:
 // ACTOR_TD3_BC adds the BC term's gradient on rows < bx.B_demo to dL/da, ACTOR_BC_ONLY also runs
-// no critic pass. The plain forms' statements are what they were.
+// no critic pass. The plain forms' statements are what they were. POP with ACTOR_TD3_BC is
+// k_td3_actor_rows_bc_pop: `a` and `bx` from the member's entry of the BC table.
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if constexpr (!POP) {
         if (a.warm.n && (int)blockIdx.y >= a.warm.y0) {  // an L2 warmer row (small grids)

@@ -84,6 +84,13 @@ class NavTd3Member(C.Structure):
     ]
 
 
+class NavTd3MemberBc(C.Structure):
+    """nav_td3_member_bc: one member's demonstration mix and BC term beside its nav_td3_member."""
+    _fields_ = [("B_demo", C.c_int64), ("n_demo", C.c_int64), ("q_weight", C.c_float),
+                ("bc_weight", C.c_float), ("idx_critic", _vp), ("idx_actor", _vp),
+                ("bc_part", _vp)]
+
+
 # (name, restype, argtypes) for every entry point of include/navenv.h
 _P = C.POINTER
 SIGNATURES = [
@@ -218,6 +225,13 @@ SIGNATURES = [
                                           C.c_uint32, C.c_int32, _vp]),
     ("nav_td3_actor_rows_pop", C.c_int, [_P(NavTd3Member), C.c_int32, C.c_int64, _vp, C.c_int64,
                                          C.c_uint32, _vp]),
+    ("nav_td3_pop_bc_table_bytes", C.c_int64, [C.c_int32]),
+    ("nav_td3_pop_bc_table_build", C.c_int, [_P(NavTd3Member), _P(NavTd3MemberBc), C.c_int32,
+                                             C.c_int64, _vp, _vp]),
+    ("nav_td3_mix_idx_pop", C.c_int, [_P(NavTd3Member), _P(NavTd3MemberBc), C.c_int32, C.c_int64,
+                                      _vp, C.c_int64, C.c_uint32, C.c_int32, _vp]),
+    ("nav_td3_actor_rows_bc_pop", C.c_int, [_P(NavTd3Member), _P(NavTd3MemberBc), C.c_int32,
+                                            C.c_int64, _vp, C.c_int64, C.c_uint32, _vp]),
     ("nav_mlp_wgrad_splits_pop", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                               C.c_int32, C.c_int64]),
     ("nav_mlp_wgrad_pop", C.c_int, [_P(NavTd3Member), C.c_int32, C.c_int64, _vp, C.c_int32,
@@ -240,7 +254,7 @@ _COUNT_FNS = {"nav_mlp_param_count", "nav_mlp_packed_count", "nav_mlp_mask_count
               "nav_mlp_row_blocks", "nav_mlp_edge_count", "nav_mlp_hidden_count",
               "nav_mlp_wgrad_splits", "nav_demo_index_res", "nav_pop_table_bytes",
               "nav_td3_pop_table_bytes", "nav_mlp_wgrad_splits_pop",
-              "nav_td3_pop_state_bytes"}
+              "nav_td3_pop_state_bytes", "nav_td3_pop_bc_table_bytes"}
 
 
 class NavError(RuntimeError):

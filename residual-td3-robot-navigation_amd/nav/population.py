@@ -24,6 +24,13 @@ and pairs the worst with the best, exploit() makes each of the worst a byte copy
 learner in one launch (nav_td3_pop_exploit: networks, packed images, Adam moments, ring rows),
 hands it the source's hyper-parameters and perturbs those named by `explore`; pbt_step() is the
 three in a row. Nothing of it runs unless called.
+
+Learning from the demonstrations per member: a member's overrides may carry demo_fraction,
+bc_weight and q_weight (TD3Config). Then every member's ring has a tail with the frame-0
+transitions of its own env groups' demonstrations; learner="members" runs each TD3._update_bc on
+its tailed ring, learner="batched" issues one nav_td3_mix_idx_pop per epoch and
+nav_td3_actor_rows_bc_pop in place of nav_td3_actor_rows_pop, from a second device table of the
+members' B_demo, tail sizes and weights. With the keys in no member's overrides nothing changes.
 """
 import ctypes as C
 import dataclasses
@@ -33,9 +40,10 @@ import math
 import torch
 
 from . import config as K
-from ._lib import (NavMlp, NavParams, NavPopScore, NavReplay, NavTd3Member, NavTestOut, lib,
-                   params_struct, ptr, stream_handle)
+from ._lib import (NavMlp, NavParams, NavPopScore, NavReplay, NavTd3Member, NavTd3MemberBc,
+                   NavTestOut, lib, params_struct, ptr, stream_handle)
 from .cem import cem_group_demo_sets
+from .demo_replay import DemoReplay
 from .fields import make_field_device
 from .td3 import TD3
 from .vec_env import ReplayRing, VecEnv
@@ -56,10 +64,27 @@ PBT_OWN_KEYS = frozenset({"initial_noise", "path_length0", "seed"})
 # the epoch count, the network shape)
 PBT_PARAM_KEYS = frozenset({"demo_factor", "noise_decay", "stuck_penalty", "stuck_threshold",
                             "goal_reward", "goal_threshold", "max_action"})
+# (bc_weight and q_weight weigh the actor's loss; demo_fraction stays out: it changes B_demo, the
+# demonstration prefix of every batch)
 PBT_TD3_KEYS = frozenset({"actor_lr", "critic_lr", "gamma", "tau", "policy_noise", "noise_clip",
-                          "max_action"})
+                          "max_action", "bc_weight", "q_weight"})
 PBT_EXPLORE_KEYS = PBT_PARAM_KEYS | PBT_TD3_KEYS
 PBT_FACTORS = (0.8, 1.25)
+# learning from the demonstrations, per member (TD3Config)
+BC_KEYS = ("demo_fraction", "bc_weight", "q_weight")
+
+
+def member_demo_groups(m, envs_per_member, envs_per_group, n_demos=K.NUM_DEMO):
+    """Member m's env groups and their demonstrations in the CEM's group-major order: (range of
+    groups, range of demonstrations, n_demos per group). A member's tail holds its own envs'
+    demonstrations, so members must own whole groups."""
+    epm, epg = int(envs_per_member), int(envs_per_group)
+    if epg < 1 or epm % epg != 0:
+        raise ValueError(f"members must own whole env groups: envs_per_member {epm} is not a "
+                         f"multiple of envs_per_group {epg}")
+    gpm = epm // epg
+    groups = range(m * gpm, (m + 1) * gpm)
+    return groups, range(groups.start * n_demos, groups.stop * n_demos)
 
 
 def state_member(t, ring):
@@ -175,8 +200,12 @@ class PopulationLearner:
     The members must agree on what the launches share: network shape, batch size,
     policy_update_delay, update_counter, the optimizers' step counts, betas and eps, and ring
     capacity and fill. Everything else (weights, seed, learning rates, gamma, tau, policy_noise,
-    noise_clip, max_action) is the member's own. Call rebuild() after changing a member's
-    hyper-parameter (cfg or an optimizer's lr) or replacing one of its buffers."""
+    noise_clip, max_action, demo_fraction, bc_weight, q_weight) is the member's own. Call
+    rebuild() after changing a member's hyper-parameter (cfg or an optimizer's lr) or replacing
+    one of its buffers. If some member learns from demonstrations (TD3.bc_on), rebuild() also
+    builds the BC table from the members' b_demo(), ring tails and weights, and update() runs
+    TD3._update_bc's schedule for all members (mix_launches counts its mix launches, each
+    member's _last_b_demo / bc_part serve its actor_loss_value() / bc_loss_value())."""
 
     def __init__(self, td3, rings, stream=None):
         self.td3, self.rings = list(td3), list(rings)
@@ -199,6 +228,13 @@ class PopulationLearner:
         self._inject = [(None, None, None)] * P
         self.table = torch.zeros(lib().nav_td3_pop_table_bytes(P), dtype=torch.uint8,
                                  device=t0.device)
+        # learning from the demonstrations (a member's demo_fraction / bc_weight / q_weight): the
+        # BC table and the members' nav_td3_member_bc array, built by rebuild() once some member
+        # has it on (None: the epochs are the plain ones), and the mix launches issued
+        self.bc_table = None
+        self.bc_members = None
+        self._mix = False
+        self.mix_launches = 0
         self.rebuild(stream)
 
     @staticmethod
@@ -270,11 +306,50 @@ class PopulationLearner:
                 t.wgrad_splits = self.wgrad_splits
                 t._B = 0
                 t._workspace(self.B)
+        inject, bc = self._inject, self._bc_members()
+        if bc is not None:
+            # every member's indices come from its idx_c / idx_a, which the mix launch fills; an
+            # explicit inject() still wins (then for all members, and no mix is launched)
+            given = [j[0] is not None or j[1] is not None for j in inject]
+            self._mix = not any(given)
+            if self._mix:
+                inject = [(t.idx_c, t.idx_a, j[2]) for t, j in zip(self.td3, inject)]
+            elif not all(j[0] is not None and j[1] is not None for j in inject):
+                raise ValueError("PopulationLearner: with demonstration learning on, inject() "
+                                 "takes both index arrays of every member or none")
+            for b, j in zip(bc, inject):
+                b.idx_critic, b.idx_actor = j[0].data_ptr(), j[1].data_ptr()
         self.members = (NavTd3Member * self.P)(*[
-            self._member(t, r, j) for t, r, j in zip(self.td3, self.rings, self._inject)])
+            self._member(t, r, j) for t, r, j in zip(self.td3, self.rings, inject)])
         lib().nav_td3_pop_table_build(self.members, self.P, self.B, self.wgrad_splits[0],
                                       self.wgrad_splits[1], ptr(self.table),
                                       stream_handle(stream))
+        self.bc_members = None
+        if bc is not None:
+            self.bc_members = (NavTd3MemberBc * self.P)(*bc)
+            if self.bc_table is None:
+                self.bc_table = torch.zeros(lib().nav_td3_pop_bc_table_bytes(self.P),
+                                            dtype=torch.uint8, device=self.td3[0].device)
+            lib().nav_td3_pop_bc_table_build(self.members, self.bc_members, self.P, self.B,
+                                             ptr(self.bc_table), stream_handle(stream))
+
+    def _bc_members(self):
+        """The members' nav_td3_member_bc entries (index pointers still unset), or None if no
+        member learns from demonstrations. A member with it off takes B_demo = 0, bc_weight = 0
+        and q_weight = 1: the plain actor loss, bit for bit."""
+        if not any(t.bc_on() for t in self.td3):
+            return None
+        out = []
+        for t, ring in zip(self.td3, self.rings):
+            b = NavTd3MemberBc()
+            b.B_demo = t.b_demo() if t.bc_on() else 0
+            b.n_demo = int(ring.tail.shape[0])
+            if b.B_demo and b.n_demo < 1:
+                raise ValueError("demo_fraction > 0 needs a replay ring with a demonstration tail")
+            b.q_weight, b.bc_weight = (t.cfg.q_weight, t.cfg.bc_weight) if t.bc_on() else (1.0, 0.0)
+            b.bc_part = t.bc_part.data_ptr()
+            out.append(b)
+        return out
 
     def _step(self, group, soft_update, s):
         """The group's weight gradients, then reduce + Adam (+ the soft updates) and the packed
@@ -302,13 +377,27 @@ class PopulationLearner:
         if size < 1:
             return
         L, s, tab = lib(), stream_handle(stream), ptr(self.table)
+        bc = self.bc_members
         for epoch in range(n):
             ctr = t0.update_counter
+            policy = epoch % t0.cfg.policy_update_delay == 0
+            if bc is not None and self._mix:
+                # TD3._update_bc's order: the epoch's mixed indices (the actor's on policy epochs
+                # only), the unchanged critic launch, then the BC form of the actor launch
+                self.mix_launches += 1
+                L.nav_td3_mix_idx_pop(self.members, bc, self.P, self.B, ptr(self.bc_table), size,
+                                      ctr, int(policy), s)
             L.nav_td3_critic_rows_pop(self.members, self.P, self.B, tab, size, ctr,
                                       self.split_twins, s)
             self._step(0, False, s)
-            if epoch % t0.cfg.policy_update_delay == 0:
-                L.nav_td3_actor_rows_pop(self.members, self.P, self.B, tab, size, ctr, s)
+            if policy:
+                if bc is not None:
+                    for t, b in zip(self.td3, bc):
+                        t._last_b_demo = int(b.B_demo)
+                    L.nav_td3_actor_rows_bc_pop(self.members, bc, self.P, self.B,
+                                                ptr(self.bc_table), size, ctr, s)
+                else:
+                    L.nav_td3_actor_rows_pop(self.members, self.P, self.B, tab, size, ctr, s)
                 self._step(1, True, s)
             for t in self.td3:
                 t.update_counter += 1
@@ -337,7 +426,17 @@ class PopulationTrainer:
             raise ValueError('learner="batched" issues one launch for all members: streams must '
                              'be 1')
         routed = [route_overrides(m) for m in self.members]
+        # learning from the demonstrations: on for a member whose demo_fraction or bc_weight is
+        # non-zero (TD3.bc_on); then every member's ring carries a tail of its own envs'
+        # demonstrations
+        self.bc = any(ck.get("demo_fraction", 0.0) != 0 or ck.get("bc_weight", 0.0) != 0
+                      for _, ck, _ in routed)
+        if not demos and any(k in ck for _, ck, _ in routed for k in BC_KEYS):
+            raise ValueError("demo_fraction / bc_weight / q_weight need demonstrations: "
+                             "demos=True")
         self.epm = int(envs_per_member)
+        if self.bc:  # members own whole env groups (ValueError otherwise)
+            member_demo_groups(0, self.epm, int(envs_per_group) if envs_per_group else self.epm)
         self.n = P * self.epm
         self.device = torch.device(device)
         self.seed = int(seed)
@@ -350,15 +449,29 @@ class PopulationTrainer:
         if demos:  # as VecTrainer: each group's demonstrations from the batched CEM
             G = (self.n + epg - 1) // epg
             firsts = torch.arange(G, device=self.device) * epg
-            pts, off = cem_group_demo_sets(self.field, self.env.region[firsts].cpu().numpy(),
-                                           self.env.goal[firsts].cpu().numpy(), self.seed,
-                                           device=self.device)
+            # (the CEM's states, actions and goals are kept for the members' DemoReplay)
+            pts, off, *self._cem = cem_group_demo_sets(
+                self.field, self.env.region[firsts].cpu().numpy(),
+                self.env.goal[firsts].cpu().numpy(), self.seed, device=self.device,
+                with_transitions=True)
             self.env.set_demo(pts, off if G > 1 else None)
+        else:
+            self._cem = None
         lo, hi = self.seed & 0xFFFFFFFF, (self.seed >> 32) & 0xFFFFFFFF
         self.params = [params_struct(seed_lo=lo, seed_hi=hi, **pk) for pk, _, _ in routed]
         cap = int(replay_capacity or max(4 * self.epm, 2 * int(batch), K.BUFFER_SIZE))
-        self.ring_rows = torch.zeros(P, cap, 8, dtype=torch.float32, device=self.device)
-        self.rings = [ReplayRing(cap, self.device, rows=self.ring_rows[m]) for m in range(P)]
+        # the members' rings, [P][cap][8]; with demonstration learning on [P][cap + tail][8]:
+        # member m's tail holds the frame-0 transitions of its own env groups' demonstrations
+        self.demo_replays = None
+        tail = 0
+        if self.bc:
+            _, d0 = member_demo_groups(0, self.epm, epg)
+            tail = len(d0) * (int(self._cem[0].shape[1]) - 1)
+        self.ring_rows = torch.zeros(P, cap + tail, 8, dtype=torch.float32, device=self.device)
+        self.rings = [ReplayRing(cap, self.device, rows=self.ring_rows[m], tail=tail)
+                      for m in range(P)]
+        if self.bc:
+            self.demo_replays = [self._member_demos(m, self.rings[m]) for m in range(P)]
         self.td3 = []
         # the weight-gradient row splits: the batched learner's fill the chip with all members'
         # tiles; "members" takes TD3's own unless wgrad_splits= asks for others (to match a
@@ -371,6 +484,8 @@ class PopulationTrainer:
             t = TD3(cfg, device=self.device, seed=int(ex.get("seed", self.seed)),
                     wgrad_splits=wgrad_splits)
             t._workspace(cfg.batch_size)  # allocated now, on the stream every later one waits for
+            if t.bc_on():
+                t.b_demo()  # validates demo_fraction / bc_weight against the batch size
             self.td3.append(t)
             sl = self.member_slice(m)
             if "initial_noise" in ex:
@@ -395,6 +510,34 @@ class PopulationTrainer:
 
     def member_slice(self, m):
         return slice(m * self.epm, (m + 1) * self.epm)
+
+    # ---- learning from the demonstrations
+    def _member_demos(self, m, ring=None):
+        """Member m's DemoReplay: the transitions of its own env groups' demonstrations with its
+        own constants, the frame-0 rows in `ring`'s tail if given."""
+        if self._cem is None:
+            raise ValueError("no demonstrations: construct with demos=True")
+        st, ac, gl = self._cem
+        _, d = member_demo_groups(m, self.epm, self.env.envs_per_group)
+        sl = slice(d.start, d.stop)
+        return DemoReplay(st[sl], ac[sl], gl[sl], self.params[m], ring=ring)
+
+    def _demos(self, m):
+        if self.demo_replays is None:
+            self.demo_replays = [self._member_demos(k) for k in range(self.P)]
+        return self.demo_replays[m]
+
+    def pretrain_bc(self, epochs, lr=None, batch=None, stream=None):
+        """VecTrainer.pretrain_bc member by member: each actor cloned on its own envs'
+        demonstrations in the acting frame (start-up work, one member's launches after another's)."""
+        for m, t in enumerate(self.td3):
+            t.pretrain_bc(self._demos(m).rows1, epochs, batch, lr, stream)
+        if self.learner is not None:
+            self.learner.rebuild(stream)
+
+    def bc_loss(self, frame=1):
+        """Each member's BC loss over every row of its demonstrations in `frame`, in order."""
+        return [t.bc_loss(self._demos(m).rows(frame)) for m, t in enumerate(self.td3)]
 
     def collect(self, stream=None):
         """Every member's action selection and tick: one launch."""
@@ -548,6 +691,14 @@ class PopulationTrainer:
             if name not in PBT_EXPLORE_KEYS:
                 raise KeyError(f"{name!r} cannot be explored: not one of the float-valued "
                                f"per-member fields {sorted(PBT_EXPLORE_KEYS)}")
+        # a clone without demonstration rows in its batches keeps bc_weight 0 (a source's own is 0
+        # then, so only a lower bound above 0 could lift it): refused as TD3.b_demo refuses it
+        if explore and float(explore.get("bc_weight", (0.0, 0.0))[0]) > 0:
+            for s in src:
+                c = self.td3[s].cfg
+                if int(round(c.demo_fraction * c.batch_size)) == 0:
+                    raise ValueError("bc_weight needs demonstration rows in the batch: member "
+                                     f"{s}'s demo_fraction * batch_size rounds to 0")
         if not src:
             return []
         if explore and rng is None:

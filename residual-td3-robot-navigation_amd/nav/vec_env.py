@@ -86,9 +86,10 @@ class ReplayRing:
                                        device=device)
             rows = self.storage[:self.capacity]
         else:
-            # (rows given: a [capacity][8] slice of a population's ring tensor, no tail)
-            assert n_tail == 0
+            # (rows given: a [capacity + tail][8] slice of a population's ring tensor)
+            assert rows.shape == (self.capacity + n_tail, 8) and rows.is_contiguous()
             self.storage = rows
+            rows = self.storage[:self.capacity]
         assert rows.shape == (self.capacity, 8) and rows.is_contiguous()
         self.rows = rows
         self.tail = self.storage[self.capacity:]

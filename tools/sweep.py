@@ -112,7 +112,11 @@ def main(argv=None):
         ap.error("--replicas must be at least 1")
     members, replica = members_of(axes, a.replicas, a.seed)
 
-    from nav.population import PopulationTrainer
+    from nav.population import BC_KEYS, PBT_EXPLORE_KEYS, PopulationTrainer
+    for name, _ in a.pbt_explore:
+        if name not in PBT_EXPLORE_KEYS:
+            ap.error(f"--pbt-explore {name}: cannot be explored; one of "
+                     f"{sorted(PBT_EXPLORE_KEYS)}")
     tr = PopulationTrainer(members, envs_per_member=a.envs_per_member, hidden=a.hidden,
                            n_hidden=a.n_hidden, batch=a.batch or a.envs_per_member,
                            updates_per_step=a.updates_per_step, seed=a.seed,
@@ -129,6 +133,8 @@ def main(argv=None):
             for ev in tr.pbt_history[seen:]:
                 print(json.dumps({"pbt": ev}), flush=True)
     for m, row in enumerate(tr.evaluate(max_steps=a.test_steps)):
+        if tr.bc:  # learning from the demonstrations: every member's three values, set or default
+            row.update({k: tr.member_value(m, k) for k in BC_KEYS})
         print(json.dumps({"member": m, "replica": replica[m], "train_steps": a.train_steps,
                           **row}), flush=True)
 
