@@ -41,6 +41,7 @@ extern "C" {
 #define NAV_TAG_TNOISE 5 /* ctr = (row, 0, 5, update)         target-smoothing noise    */
 #define NAV_TAG_TEST 6   /* ctr = (0, env, 6, episode)        test-episode start draw   */
 #define NAV_TAG_DEMO 7   /* ctr = (i, 0, 7, update)           demonstration row index   */
+#define NAV_TAG_PER 8    /* ctr = (b, 0, 8, 2*update [+1])    prioritised sample draw   */
 
 /* Constants of constants.py / robot.py as a POD (defaults in nav_default_params). */
 typedef struct nav_params {
@@ -433,6 +434,23 @@ int nav_td3_critic_rows(const nav_mlp* target_actor, const nav_mlp* target_criti
                         float* const* acts, uint32_t save_mask, uint16_t* const* masks,
                         int32_t row_backward, float* const* dz, uint32_t dz_save_mask,
                         int32_t split_twins, void* stream);
+/* nav_td3_critic_rows with per-row importance weights (prioritised replay): every argument of
+ * nav_td3_critic_rows in order, then w [B] and td_abs (two [B] arrays, both required). With
+ * e = q_i - y of row b: dq[i][b] = (e * norm) * w[b], loss_part[i] holds block sums of
+ * (e * e) * w[b], td_abs[i][b] = fabsf(e). Everything downstream in the launch reads the
+ * weighted dq (the Wo / bo partials, the row backward, and what nav_mlp_wgrad later reads from
+ * dq). Both twin forms and row_backward 0 / 1 as the plain form; with w == 1.0f every output the
+ * plain form also writes is bit-identical to it. NAV_EINVAL: w or td_abs (or either array) NULL. */
+int nav_td3_critic_rows_w(const nav_mlp* target_actor, const nav_mlp* target_critics,
+                          const nav_mlp* critics, const nav_replay* replay, int64_t size,
+                          int64_t B, const int64_t* idx, uint32_t seed_lo, uint32_t seed_hi,
+                          uint32_t counter, const float* eps, float policy_noise,
+                          float noise_clip, float max_action, float gamma, float* batch,
+                          float* const* dq, float* const* loss_part, float* const* edge_slabs,
+                          float* const* acts, uint32_t save_mask, uint16_t* const* masks,
+                          int32_t row_backward, float* const* dz, uint32_t dz_save_mask,
+                          int32_t split_twins, const float* w, float* const* td_abs,
+                          void* stream);
 /* train_actor's row-local part (robot.py:382-390) in one launch: sample rows (Philox
  * NAV_TAG_SAMPLE at 2*counter + 1, or idx) into batch [B][8]; actor forward on s (ReLU bits to
  * masks_actor, activations to acts for save_mask bits; the top layer's dWo partials come
@@ -599,6 +617,48 @@ int nav_td3_mix_idx(int64_t size, int64_t B, int64_t B_demo, int64_t demo_base, 
 int nav_demo_transitions(const nav_params* p, int32_t n_demo, int32_t T, const float* states,
                          const float* actions, const double* goal, int32_t frame, float* rows,
                          void* stream);
+/* ---- Prioritised replay (Schaul et al. 2016, the proportional variant) ----
+ * One priority per ring row, 32-bit fixed point with 16 fractional bits (65536 = 1.0); every sum
+ * is an exact uint64, so a sampled index is a pure function of the stored integers and the Philox
+ * words: it does not depend on chunk sizes, the hierarchy's shape or a summation order. */
+typedef struct nav_per {
+    uint32_t* pri;    /* [capacity] priorities; rows >= size are never read as priorities */
+    uint64_t* sums;   /* workspace, nav_per_sums_count(capacity) words (layout private) */
+    uint32_t* stat;   /* [4]: [0] running max priority ever written, [1] min over [0,size) at
+                         the last nav_per_sums, [2..3] reserved (0) */
+    int64_t capacity;
+} nav_per;
+/* Every entry point below checks on the host, before any HIP call (NAV_EINVAL): a NULL struct or
+ * member, capacity < 1, and what each one names. */
+/* uint64 words of the `sums` workspace (NAV_EINVAL: capacity < 1). */
+int64_t nav_per_sums_count(int64_t capacity);
+/* pri = 0, stat = {65536, 0, 0, 0}. */
+int nav_per_init(const nav_per* per, void* stream);
+/* Rows (pos + i) mod capacity, i < n, receive the current stat[0] (read on the device: no host
+ * sync); n = 0 is a no-op. NAV_EINVAL: n < 0 or > capacity, pos outside [0, capacity). */
+int nav_per_stamp(const nav_per* per, int64_t pos, int64_t n, void* stream);
+/* Rebuild every level of the sum hierarchy, the total S and the minimum (stat[1]) from
+ * pri[0..size); rows at or beyond size contribute nothing, whatever their bits hold.
+ * NAV_EINVAL: size < 1 or > capacity. */
+int nav_per_sums(const nav_per* per, int64_t size, void* stream);
+/* One launch, three arrays (any may be NULL, as nav_td3_mix_idx). Row b: r64 = (w.y << 32) | w.x
+ * of Philox NAV_TAG_PER at ctr = (b, 0, 8, 2*counter) (idx_actor: 2*counter + 1), t = the high 64
+ * bits of r64 * S, idx = min{k : P_k > t} with P_k = sum_{j<=k} pri[j] over [0, size), and
+ * w_critic[b] = (float)pow((double)stat[1] / (double)pri[idx_critic[b]], (double)beta): the usual
+ * (N p_k / S)^-beta over its maximum, in (0, 1]; exactly 1.0f when all priorities are equal.
+ * Needs nav_per_sums since the last write to pri. Draws are independent (not stratified).
+ * NAV_EINVAL: size < 1 or > capacity, B < 1, beta < 0 or NaN, w_critic without idx_critic. */
+int nav_per_sample(const nav_per* per, int64_t size, int64_t B, uint32_t seed_lo,
+                   uint32_t seed_hi, uint32_t counter, float beta, int64_t* idx_critic,
+                   float* w_critic, int64_t* idx_actor, void* stream);
+/* The new priorities of the sampled rows: for b < B, m = 0.5*((double)|td1[b]| + (double)|td2[b]|)
+ * + (double)eps and q = (uint32)clamp(floor(pow(m, (double)alpha) * 65536.0 + 0.5), 1, 2^31 - 1)
+ * (NaN gives 1, +inf 2^31 - 1: no stored priority is ever 0). pri[idx[b]] becomes the maximum of
+ * q over all b' with idx[b'] == idx[b] (the old value is replaced, not maxed with; deterministic
+ * with duplicates), stat[0] = max(stat[0], all q). idx in [0, capacity).
+ * NAV_EINVAL: B < 1, NULL idx / td1 / td2, alpha <= 0 or NaN, eps < 0 or NaN. */
+int nav_per_update(const nav_per* per, int64_t B, const int64_t* idx, const float* td1,
+                   const float* td2, float alpha, float eps, void* stream);
 /* Fill / strided copy helpers of the TD3 glue (robot.py:329-339, 386-390). */
 int nav_fill(float* x, int64_t n, float value, void* stream);
 int nav_strided_copy(const float* src, int32_t ld_src, int32_t col_src, float* dst, int32_t ld_dst,

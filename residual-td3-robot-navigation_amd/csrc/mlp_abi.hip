@@ -4,7 +4,7 @@
 #include "mlp_rows_role.h"
 #include "pop_host.h"
 
-// the 5 x 8 launcher objects' dispatchers
+// the 6 x 8 launcher objects' dispatchers
 #define NAV_ROWS_DECL(role, nt) rows_fn NAV_ROWS_FN(role, nt);
 #define NAV_ROWS_DECL_ROLE(role) NAV_ROWS_NTS(NAV_ROWS_DECL, role)
 NAV_ROWS_ROLES(NAV_ROWS_DECL_ROLE)
@@ -584,6 +584,30 @@ int nav_td3_critic_rows(const nav_mlp* target_actor, const nav_mlp* target_criti
                                     a);
     if (rc) return rc;
     return rows_dispatch(a.actor_t.hp, FAM_CRITIC, 0, 0, &a, 1, a.B, S(stream));
+}
+
+int nav_td3_critic_rows_w(const nav_mlp* target_actor, const nav_mlp* target_critics,
+                          const nav_mlp* critics, const nav_replay* replay, int64_t size,
+                          int64_t B, const int64_t* idx, uint32_t seed_lo, uint32_t seed_hi,
+                          uint32_t counter, const float* eps, float policy_noise,
+                          float noise_clip, float max_action, float gamma, float* batch,
+                          float* const* dq, float* const* loss_part, float* const* edge_slabs,
+                          float* const* acts, uint32_t save_mask, uint16_t* const* masks,
+                          int32_t row_backward, float* const* dz, uint32_t dz_save_mask,
+                          int32_t split_twins, const float* w, float* const* td_abs,
+                          void* stream) {
+    CriticRowsWArgs x{};
+    if (!w || !td_abs || !td_abs[0] || !td_abs[1]) return NAV_EINVAL;
+    const int rc = critic_rows_args(target_actor, target_critics, critics, replay, size, B, idx,
+                                    seed_lo, seed_hi, counter, eps, policy_noise, noise_clip,
+                                    max_action, gamma, batch, dq, loss_part, edge_slabs, acts,
+                                    save_mask, masks, row_backward, dz, dz_save_mask, split_twins,
+                                    x.r);
+    if (rc) return rc;
+    x.per.w = w;
+    x.per.td_abs[0] = td_abs[0];
+    x.per.td_abs[1] = td_abs[1];
+    return rows_dispatch(x.r.actor_t.hp, FAM_CRITIC_W, 0, 0, &x, 1, x.r.B, S(stream));
 }
 
 int nav_td3_actor_rows(const nav_mlp* actor, const nav_mlp* critic, const nav_replay* replay,

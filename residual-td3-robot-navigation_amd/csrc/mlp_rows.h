@@ -878,10 +878,13 @@ NAV_DEV void wo_grad_regs(const MlpDev& net, const f32x16 (&top)[RT][2], const f
 // row (robot.py:341-345, from the caller), mse_loss's gradient dq = (q - yt) * 2/B, the block's
 // sum of (q - y)^2, and the output layer's gradient partials dWo = dq^T h_top, dbo = sum dq while
 // h_top is still in LDS. `red` = the [2][PARTS][TM] partial-sum scratch (second half reused).
-template <int NT, int RT>
+// WEIGHTED (k_td3_critic_rows_w, prioritised replay): the row's importance weight wrow[r] scales
+// dq and the loss term, and |q - yt| goes to td_abs[r]; off, the statements are the plain ones.
+template <int NT, int RT, bool WEIGHTED = false>
 NAV_DEV void loss_epilogue(const MlpDev& net, const f32x16 (&top)[RT][2], float* red,
                            int64_t row0, int64_t M, float yt, float norm, float* dq,
-                           float* loss_slot, float* es) {
+                           float* loss_slot, float* es, const float* wrow = nullptr,
+                           float* td_abs = nullptr) {
     constexpr int TM = RT * 32;
     const int tid = threadIdx.x;
     const int64_t r = row0 + tid;
@@ -891,6 +894,12 @@ NAV_DEV void loss_epilogue(const MlpDev& net, const f32x16 (&top)[RT][2], float*
         const float e = y - yt;
         dqv = e * norm;
         e2 = e * e;
+        if constexpr (WEIGHTED) {
+            const float wr = wrow[r];
+            dqv *= wr;
+            e2 *= wr;
+            td_abs[r] = fabsf(e);
+        }
         dq[r] = dqv;
     }
     float* dqs = red + kWaves * TM;  // [TM] dq (past output 0's partials), then the wave sums
@@ -1903,16 +1912,44 @@ struct RowsPop {
 // token for token what they were (its machine code is pinned, tools/isa_diff.py), the population
 // form (POP) reads `a` from the member's table entry and the launch's values from `pv` (the
 // entry's rsize, counters, split_twins and warm list are then unused).
+// The weighted form (nav_td3_critic_rows_w, prioritised replay): the plain arguments and, beside
+// them, the rows' importance weights and the |TD error| outputs. Not in CriticRowsArgs: the
+// population table stores that struct per member.
+struct CriticPerExtra {
+    const float* w;      // [B] importance weights
+    float* td_abs[2];    // [B] |q_i - y| per online critic
+};
+struct CriticRowsWArgs {
+    CriticRowsArgs r;
+    CriticPerExtra per;
+};
+static_assert(sizeof(CriticRowsWArgs) <= 4096, "kernel argument size");
+
 template <int NT, int RT, int CBM>
 __global__ __launch_bounds__(kBlock, 1) void k_td3_critic_rows(CriticRowsArgs a) {
     constexpr bool POP = false;
     constexpr RowsPop pv{};
+    constexpr bool WEIGHTED = false;
+    constexpr CriticPerExtra px{};
 #include "td3_critic_rows_body.inc"
 }
 template <int NT, int RT, int CBM>
 __global__ __launch_bounds__(kBlock, 1) void k_td3_critic_rows_pop(RowsPop pv) {
     constexpr bool POP = true;
+    constexpr bool WEIGHTED = false;
+    constexpr CriticPerExtra px{};
     const CriticRowsArgs& a = static_cast<const CriticRowsArgs*>(pv.table)[blockIdx.z];
+#include "td3_critic_rows_body.inc"
+}
+// the weighted form (WEIGHTED: loss_epilogue scales dq and the loss term by px.w and writes
+// px.td_abs; everything downstream reads the weighted dq)
+template <int NT, int RT, int CBM>
+__global__ __launch_bounds__(kBlock, 1) void k_td3_critic_rows_w(CriticRowsWArgs x) {
+    constexpr bool POP = false;
+    constexpr RowsPop pv{};
+    constexpr bool WEIGHTED = true;
+    const CriticRowsArgs& a = x.r;
+    const CriticPerExtra& px = x.per;
 #include "td3_critic_rows_body.inc"
 }
 
@@ -2024,7 +2061,7 @@ int row_tiles_for(int64_t M, bool tick) { return (!tick && M <= kSmallRows) ? 1 
 // them through nav_mlp_rows_<role>_<NT>(). Argument structs travel as const void* (same definitions).
 enum {
     FAM_FWD = 0, FAM_BWD = 1, FAM_CRITIC = 2, FAM_ACTOR = 3, FAM_TEST = 4, FAM_TEST_POP = 5,
-    FAM_CRITIC_POP = 6, FAM_ACTOR_POP = 7, FAM_ACTOR_BC = 8, FAM_ACTOR_BC_POP = 9
+    FAM_CRITIC_POP = 6, FAM_ACTOR_POP = 7, FAM_ACTOR_BC = 8, FAM_ACTOR_BC_POP = 9, FAM_CRITIC_W = 10
 };
 
 }  // namespace

@@ -1,5 +1,5 @@
 // mlp_rows_nt.hip — the launchers of the row kernels (mlp_rows.h) of one hidden width, hp = 32 *
-// NAV_MLP_PART, and one role (NAV_MLP_ROLE, mlp_rows_role.h): 8 x 5 independent objects, so make
+// NAV_MLP_PART, and one role (NAV_MLP_ROLE, mlp_rows_role.h): 8 x 6 independent objects, so make
 // -j compiles the heavy template instantiations in parallel. Each exports one dispatcher,
 // nav_mlp_rows_<role>_<NT>(), that mlp_abi.hip calls; the role decides which kernels the object
 // instantiates.
@@ -79,6 +79,20 @@ void launch_actor_rows(const ActorRowsArgs& a, hipStream_t st) {
     launch_k(k, dim3(gx, 1u + wy), actor_rows_lds(TM, NT * 32), st, w);
 }
 
+// the weighted form (prioritised replay): the plain form's grid, warmers and LDS
+template <int NT, int RT>
+void launch_critic_rows_w(const CriticRowsWArgs& a, hipStream_t st) {
+    constexpr int TM = RT * 32;
+    auto k = a.r.critic[0].n_hidden == 1 ? k_td3_critic_rows_w<NT, RT, 0>
+                                         : k_td3_critic_rows_w<NT, RT, 1>;
+    const unsigned gx = row_blocks(a.r.B, TM), gy = a.r.split_twins ? 2u : 1u;
+    CriticRowsWArgs w = a;
+    const WarmNet nets[] = {{a.r.actor_t, true}, {a.r.critic_t[0], true}, {a.r.critic_t[1], true},
+                            {a.r.critic[0], false}, {a.r.critic[1], false}};
+    const unsigned wy = set_warmers(w.r.warm, nets, 5, gx, gy);
+    launch_k(k, dim3(gx, gy + wy), critic_rows_lds(TM, NT * 32), st, w);
+}
+
 // the BC forms; bc_only warms the actor's images alone
 template <int NT, int RT>
 void launch_actor_rows_bc(const ActorRowsBcArgs& a, hipStream_t st) {
@@ -131,7 +145,9 @@ void launch_test(const TestArgs& a, hipStream_t st) {
 template <int NT, int RT, int ROLE>
 int rows_rt(int fam, int in_mode, int out_mode, const void* args, int n_nets, hipStream_t st) {
     if (rows_role(fam, out_mode) != ROLE) return NAV_EINVAL;
-    if constexpr (ROLE == ROLE_BC) {
+    if constexpr (ROLE == ROLE_PER) {
+        launch_critic_rows_w<NT, RT>(*static_cast<const CriticRowsWArgs*>(args), st);
+    } else if constexpr (ROLE == ROLE_BC) {
         launch_actor_rows_bc<NT, RT>(*static_cast<const ActorRowsBcArgs*>(args), st);
     } else if constexpr (ROLE == ROLE_BCPOP) {
         launch_actor_rows_bc_pop<NT, RT>(*static_cast<const RowsPopLaunch*>(args), st);

@@ -1,5 +1,6 @@
 // k_td3_critic_rows' statements (mlp_rows.h includes this once per form: `a` the arguments,
-// POP and `pv` the population form's flag and launch values)
+// POP and `pv` the population form's flag and launch values, WEIGHTED and `px` the weighted
+// form's flag and extras: k_td3_critic_rows_w)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if constexpr (!POP) {
         if (a.warm.n && (int)blockIdx.y >= a.warm.y0) {  // an L2 warmer row (small grids)
@@ -138,8 +139,12 @@
             if (q == 0 && !a.split_twins) l0_on = load_l0<NT>(a.critic[1]);
         }
         float* es = a.eslab[q] ? a.eslab[q] + (int64_t)blockIdx.x * a.ecount : nullptr;
-        loss_epilogue<NT, RT>(a.critic[q], top, red, row0, B, yt, a.norm, a.dq[q],
-                              a.loss_part[q] + blockIdx.x, es);
+        if constexpr (WEIGHTED)
+            loss_epilogue<NT, RT, true>(a.critic[q], top, red, row0, B, yt, a.norm, a.dq[q],
+                                        a.loss_part[q] + blockIdx.x, es, px.w, px.td_abs[q]);
+        else
+            loss_epilogue<NT, RT>(a.critic[q], top, red, row0, B, yt, a.norm, a.dq[q],
+                                  a.loss_part[q] + blockIdx.x, es);
         __syncthreads();
         NAV_MARK(28 + 14 * q);
         if (a.row_backward) {

@@ -46,6 +46,11 @@ class NavReplay(C.Structure):
     _fields_ = [("rows", _vp), ("capacity", C.c_int64)]
 
 
+class NavPer(C.Structure):
+    """nav_per: the priority store beside a replay ring (prioritised replay)."""
+    _fields_ = [("pri", _vp), ("sums", _vp), ("stat", _vp), ("capacity", C.c_int64)]
+
+
 class NavMlp(C.Structure):
     _fields_ = [
         ("d_in", C.c_int32), ("d_out", C.c_int32), ("hidden", C.c_int32),
@@ -165,6 +170,12 @@ SIGNATURES = [
                                       _vp, _P(_vp), _P(_vp), _P(_vp), _P(_vp), C.c_uint32,
                                       _P(_vp), C.c_int32, _P(_vp), C.c_uint32, C.c_int32,
                                       _vp]),
+    ("nav_td3_critic_rows_w", C.c_int, [_P(NavMlp), _P(NavMlp), _P(NavMlp), _P(NavReplay),
+                                        C.c_int64, C.c_int64, _vp, C.c_uint32, C.c_uint32,
+                                        C.c_uint32, _vp, C.c_float, C.c_float, C.c_float,
+                                        C.c_float, _vp, _P(_vp), _P(_vp), _P(_vp), _P(_vp),
+                                        C.c_uint32, _P(_vp), C.c_int32, _P(_vp), C.c_uint32,
+                                        C.c_int32, _vp, _P(_vp), _vp]),
     ("nav_td3_actor_rows", C.c_int, [_P(NavMlp), _P(NavMlp), _P(NavReplay), C.c_int64,
                                      C.c_int64, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp,
                                      _vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp,
@@ -176,6 +187,14 @@ SIGNATURES = [
     ("nav_td3_mix_idx", C.c_int, [C.c_int64] * 5 + [C.c_uint32] * 3 + [_vp, _vp, _vp]),
     ("nav_demo_transitions", C.c_int, [_P(NavParams), C.c_int32, C.c_int32, _vp, _vp, _vp,
                                        C.c_int32, _vp, _vp]),
+    ("nav_per_sums_count", C.c_int64, [C.c_int64]),
+    ("nav_per_init", C.c_int, [_P(NavPer), _vp]),
+    ("nav_per_stamp", C.c_int, [_P(NavPer), C.c_int64, C.c_int64, _vp]),
+    ("nav_per_sums", C.c_int, [_P(NavPer), C.c_int64, _vp]),
+    ("nav_per_sample", C.c_int, [_P(NavPer), C.c_int64, C.c_int64, C.c_uint32, C.c_uint32,
+                                 C.c_uint32, C.c_float, _vp, _vp, _vp, _vp]),
+    ("nav_per_update", C.c_int, [_P(NavPer), C.c_int64, _vp, _vp, _vp, C.c_float, C.c_float,
+                                 _vp]),
     ("nav_mlp_mask_count", C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
     ("nav_mlp_row_blocks", C.c_int64, [C.c_int64]),
     ("nav_mlp_edge_count", C.c_int64, [C.c_int32] * 4),
@@ -254,7 +273,8 @@ _COUNT_FNS = {"nav_mlp_param_count", "nav_mlp_packed_count", "nav_mlp_mask_count
               "nav_mlp_row_blocks", "nav_mlp_edge_count", "nav_mlp_hidden_count",
               "nav_mlp_wgrad_splits", "nav_demo_index_res", "nav_pop_table_bytes",
               "nav_td3_pop_table_bytes", "nav_mlp_wgrad_splits_pop",
-              "nav_td3_pop_state_bytes", "nav_td3_pop_bc_table_bytes"}
+              "nav_td3_pop_state_bytes", "nav_td3_pop_bc_table_bytes",
+              "nav_per_sums_count"}
 
 
 class NavError(RuntimeError):

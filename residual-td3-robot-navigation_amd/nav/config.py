@@ -81,4 +81,10 @@ class TD3Config:
     bc_weight: float = 0.0
     q_weight: float = 1.0
     demo_fraction: float = 0.0
+    # prioritised replay (off by default, per_alpha == 0): batches are drawn in proportion to
+    # priority (|TD error| + per_eps)^per_alpha and the critics' loss carries the importance
+    # weights (N p_k / S)^-per_beta over their maximum; per_beta is read every epoch
+    per_alpha: float = 0.0
+    per_beta: float = 0.4
+    per_eps: float = 1e-6
     net: NetConfig = field(default_factory=NetConfig)

@@ -426,6 +426,10 @@ class PopulationTrainer:
             raise ValueError('learner="batched" issues one launch for all members: streams must '
                              'be 1')
         routed = [route_overrides(m) for m in self.members]
+        for m, (_, ck, _) in enumerate(routed):
+            if ck.get("per_alpha", 0.0) != 0:
+                raise ValueError("prioritised replay (per_alpha > 0) is not available to "
+                                 f"population members: member {m}")
         # learning from the demonstrations: on for a member whose demo_fraction or bc_weight is
         # non-zero (TD3.bc_on); then every member's ring carries a tail of its own envs'
         # demonstrations

@@ -84,6 +84,18 @@ class TD3:
                 raise ValueError("grad_hook must carry an int world_size >= 1: it SUM-all-reduces "
                                  "the gradient bucket and Adam divides by world_size")
             self.grad_div = float(ws)
+        # prioritised replay (cfg.per_alpha > 0; off by default): what it does not combine with
+        # is refused here
+        self.per_launches = 0    # nav_per_* calls issued (0 with the feature off)
+        if c.per_alpha < 0 or c.per_alpha != c.per_alpha:
+            raise ValueError("per_alpha must be >= 0 (0 = prioritised replay off)")
+        if self.per_on():
+            if self.bc_on():
+                raise ValueError("prioritised replay (per_alpha > 0) does not combine with "
+                                 "demo_fraction / bc_weight")
+            if grad_hook is not None:
+                raise ValueError("prioritised replay (per_alpha > 0) does not combine with a "
+                                 "grad_hook (shared policy)")
         # row splits of the weight-gradient launches, (critic twins, actor); None = as many as
         # fill the chip (nav_mlp_wgrad_splits; tuning only)
         self.wgrad_splits = wgrad_splits
@@ -125,6 +137,10 @@ class TD3:
         self.idx_c = torch.zeros(B, dtype=torch.int64, device=d)
         self.idx_a = torch.zeros(B, dtype=torch.int64, device=d)
         self.bc_part = f(self.nblk)
+        # prioritised replay: the batch's importance weights and the twins' |TD errors|
+        if self.per_on():
+            self.w_per, self.w_one = f(B), torch.ones(B, dtype=torch.float32, device=d)
+            self.td_abs1, self.td_abs2 = f(B), f(B)
         ec = L.nav_mlp_edge_count(4, 1, hp, nh)
         self.eslab1, self.eslab2 = f(self.nblk, ec), f(self.nblk, ec)
         self.eslab_a = f(self.nblk, L.nav_mlp_edge_count(2, 2, hp, nh))
@@ -187,7 +203,7 @@ class TD3:
         if B != self._B:
             self._workspace(B)
         key = (B, self.seed, c.policy_noise, c.noise_clip, c.max_action, c.gamma, c.tau,
-               self.split_twins, c.bc_weight, c.q_weight, c.demo_fraction)
+               self.split_twins, c.bc_weight, c.q_weight, c.demo_fraction, c.per_alpha)
         if self._st is not None and self._st_key == key:
             return self._st
         c1, c2, a = self.critic_network_1, self.critic_network_2, self.actor_network
@@ -307,6 +323,16 @@ class TD3:
                   self.update_counter, ptr(eps), *st["cr_tail"], s)
         return st["c"]
 
+    def _critic_rows_w(self, replay, idx, eps, w, s):
+        # the weighted form of _critic_rows (prioritised replay): dq and the loss carry w, the
+        # twins' |TD errors| go to td_abs1 / td_abs2
+        st = self._static()
+        self._run("critic_rows_w", st["cr_work"], lib().nav_td3_critic_rows_w, *st["cr_head"],
+                  self._replay_ref(replay), len(replay), self._B, ptr(idx), *st["seed"],
+                  self.update_counter, ptr(eps), *st["cr_tail"], ptr(w),
+                  parr(self.td_abs1, self.td_abs2), s)
+        return st["c"]
+
     def train_critic(self, replay, idx=None, eps=None, stream=None):
         s = stream_handle(stream)
         # both critics' weight gradients, then reduce + Adam: one launch each
@@ -369,6 +395,50 @@ class TD3:
         rows (0 without any), synchronising."""
         n = self._last_b_demo
         return (self.bc_part.double().sum() / n).item() if n else 0.0
+
+    # ---- prioritised replay
+    def per_on(self):
+        return self.cfg.per_alpha != 0
+
+    def _update_per(self, replay, n, idx_fn, eps_fn, stream, track_losses):
+        """_update with prioritised replay: per epoch the ring's sum hierarchy (nav_per_sums),
+        one nav_per_sample (both batches' indices from the priorities, the critic batch's
+        importance weights), the weighted critic launch, the weight gradients, reduce and Adam as
+        ever, nav_per_update with the epoch's |TD errors|, and on a policy epoch the unchanged
+        actor launch on idx_actor (its loss unweighted). An explicit idx_fn still wins: the
+        weights are then 1 and the priorities are still updated."""
+        c, L = self.cfg, lib()
+        if getattr(replay, "pri", None) is None:
+            raise ValueError("per_alpha > 0 needs a replay ring with priorities "
+                             "(ReplayRing(priorities=True))")
+        self._static()
+        s = stream_handle(stream)
+        pd, B = replay.per_ref(), self._B
+        for epoch in range(n):
+            policy = epoch % c.policy_update_delay == 0
+            self._run("per_sums", 4.0 * len(replay), L.nav_per_sums, pd, len(replay), s)
+            if idx_fn:
+                idx_c, idx_a, w = idx_fn(), (idx_fn() if policy else None), self.w_one
+                self.per_launches += 1
+            else:
+                idx_c, idx_a, w = self.idx_c, (self.idx_a if policy else None), self.w_per
+                self._run("per_sample", 16.0 * B, L.nav_per_sample, pd, len(replay), B,
+                          *self._st["seed"], self.update_counter, float(c.per_beta), ptr(idx_c),
+                          ptr(w), ptr(idx_a), s)
+                self.per_launches += 2
+            g = self._critic_rows_w(replay, idx_c, eps_fn() if eps_fn else None, w, s)
+            self._step(g, s, stream)
+            self._run("per_update", 20.0 * B, L.nav_per_update, pd, B, ptr(idx_c),
+                      ptr(self.td_abs1), ptr(self.td_abs2), float(c.per_alpha), float(c.per_eps),
+                      s)
+            self.per_launches += 1
+            if track_losses:
+                self.critic_losses.append(sum(self.critic_loss_values()) / 2)
+            if policy:
+                self.train_actor(replay, idx=idx_a, stream=stream, soft_update=True)
+                if track_losses:
+                    self.actor_losses.append(self.actor_loss_value())
+            self.update_counter += 1
 
     # ---- learning from demonstrations
     def bc_on(self):
@@ -490,6 +560,8 @@ class TD3:
         if self.bc_on():
             return self._update_bc(replay, n, idx_fn, eps_fn, stream, track_losses,
                                    collect_ready)
+        if self.per_on():
+            return self._update_per(replay, n, idx_fn, eps_fn, stream, track_losses)
         for epoch in range(n):
             if (collect_ready is not None and epoch == n - 1 and self.grad_hook is not None and
                     epoch % self.cfg.policy_update_delay != 0):

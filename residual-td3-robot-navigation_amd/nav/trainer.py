@@ -28,11 +28,16 @@ class VecTrainer:
     def __init__(self, n_envs=65536, hidden=256, n_hidden=2, batch=32768, updates_per_step=2,
                  replay_capacity=None, seed=K.RANDOM_SEED, envs_per_group=1024, demos=True,
                  device="cuda", field=None, grad_hook=None, fuse_tick=True, overlap_collect=False,
-                 demo_fraction=0.0, bc_weight=0.0, q_weight=1.0, demo_rows=None):
+                 demo_fraction=0.0, bc_weight=0.0, q_weight=1.0, demo_rows=None,
+                 per_alpha=0.0, per_beta=0.4, per_eps=1e-6):
         """demo_fraction / bc_weight / q_weight: learning from the demonstrations (TD3Config; off
         by default). With demo_fraction or bc_weight non-zero the CEM demonstrations' transitions
         sit in a tail behind the replay ring and a share of every batch is drawn from it (needs
-        demos=True, or demo_rows = (frame-0 rows, frame-1 rows) from a checkpoint)."""
+        demos=True, or demo_rows = (frame-0 rows, frame-1 rows) from a checkpoint).
+        per_alpha / per_beta / per_eps: prioritised replay (TD3Config; off at per_alpha == 0).
+        On, the ring carries one priority per row, every tick stamps its rows with the running
+        maximum, and batches are drawn in proportion to priority. Not with demo_fraction /
+        bc_weight, a grad_hook or overlap_collect (ValueError)."""
         self.n = int(n_envs)
         self.device = torch.device(device)
         self.seed = int(seed)
@@ -57,7 +62,11 @@ class VecTrainer:
         cfg = K.TD3Config(batch_size=int(batch), num_epochs=int(updates_per_step),
                           net=K.NetConfig(hidden=hidden, n_hidden=n_hidden),
                           bc_weight=float(bc_weight), q_weight=float(q_weight),
-                          demo_fraction=float(demo_fraction))
+                          demo_fraction=float(demo_fraction), per_alpha=float(per_alpha),
+                          per_beta=float(per_beta), per_eps=float(per_eps))
+        if cfg.per_alpha != 0 and overlap_collect:
+            raise ValueError("prioritised replay (per_alpha > 0) does not combine with "
+                             "overlap_collect")
         self.td3 = TD3(cfg, device=self.device, seed=self.seed, grad_hook=grad_hook)
         cap = replay_capacity or max(4 * self.n, 2 * int(batch), K.BUFFER_SIZE)
         # the demonstration transitions: in the ring's tail when the learner draws from them,
@@ -75,7 +84,7 @@ class VecTrainer:
             else:
                 raise ValueError("demo_fraction / bc_weight need demonstrations: demos=True")
         else:
-            self.replay = ReplayRing(cap, self.device)
+            self.replay = ReplayRing(cap, self.device, priorities=self.td3.per_on())
             if demo_rows is not None:
                 self.demo_replay = DemoReplay.from_rows(demo_rows[0].to(self.device),
                                                         demo_rows[1])
@@ -203,7 +212,7 @@ class VecTrainer:
         Adam moments, counters) and the step counter that keys the exploration noise. A trainer
         restored from it continues bit for bit as the original would have."""
         e = self.env
-        return {
+        sd = {
             "meta": {"n_envs": self.n, "seed": self.seed, "envs_per_group": e.envs_per_group,
                      "hidden": self.td3.actor_network.hidden,
                      "n_hidden": self.td3.actor_network.n_hidden,
@@ -220,6 +229,11 @@ class VecTrainer:
                        "size": self.replay.size},
             "td3": self.td3.state_dict(),
         }
+        if self.td3.per_on():  # prioritised replay: its hyper-parameters and the priority store
+            c = self.td3.cfg
+            sd["meta"].update(per_alpha=c.per_alpha, per_beta=c.per_beta, per_eps=c.per_eps)
+            sd["replay"].update(pri=self.replay.pri.cpu(), stat=self.replay.stat.cpu())
+        return sd
 
     def load_state_dict(self, sd):
         m = sd["meta"]
@@ -233,6 +247,10 @@ class VecTrainer:
         self.replay.rows.copy_(sd["replay"]["rows"].to(self.device))
         self.replay.position = int(sd["replay"]["position"])
         self.replay.size = int(sd["replay"]["size"])
+        if self.td3.per_on():
+            self.replay.pri.copy_(sd["replay"]["pri"].to(self.device))
+            self.replay.stat.copy_(sd["replay"]["stat"].to(self.device))
+            self.td3.cfg.per_beta = float(m["per_beta"])
         self.td3.load_state_dict(sd["td3"])
         self.steps = int(m["steps"])
         self.updates_per_step = int(m["updates_per_step"])
@@ -251,7 +269,9 @@ class VecTrainer:
                 field=sd["field"].to(device), grad_hook=grad_hook,
                 demo_fraction=m.get("demo_fraction", 0.0), bc_weight=m.get("bc_weight", 0.0),
                 q_weight=m.get("q_weight", 1.0),
-                demo_rows=None if dr is None else (dr["rows0"], dr["rows1"]))
+                demo_rows=None if dr is None else (dr["rows0"], dr["rows1"]),
+                per_alpha=m.get("per_alpha", 0.0), per_beta=m.get("per_beta", 0.4),
+                per_eps=m.get("per_eps", 1e-6))
         t.load_state_dict(sd)
         return t
 

@@ -9,7 +9,7 @@ import torch
 
 from . import config as K
 from . import prof
-from ._lib import (NavEnvSoa, NavReplay, NavStepOut, NavTestOut, lib, params_struct, ptr,
+from ._lib import (NavEnvSoa, NavPer, NavReplay, NavStepOut, NavTestOut, lib, params_struct, ptr,
                    require_gpu, stream_handle)
 
 
@@ -75,7 +75,7 @@ class ReplayRing:
     """ReplayBuffer (robot.py:58-124) as a device ring of 32-byte rows
     (s0 s1 a0 a1 r s'0 s'1 done, float32)."""
 
-    def __init__(self, capacity, device="cuda", rows=None, tail=0):
+    def __init__(self, capacity, device="cuda", rows=None, tail=0, priorities=False):
         self.capacity = int(capacity)
         n_tail = int(tail)
         if rows is None:
@@ -95,9 +95,37 @@ class ReplayRing:
         self.tail = self.storage[self.capacity:]
         self.position = 0  # next write slot (robot.py:77)
         self.size = 0
+        # prioritised replay: one u32 fixed-point priority per ring row (int32 storage), the sum
+        # hierarchy's workspace and the four stat words (nav_per); none without `priorities`
+        self.pri = self.sums = self.stat = None
+        self._per = None
+        if priorities:
+            dev = self.rows.device
+            self.pri = torch.zeros(self.capacity, dtype=torch.int32, device=dev)
+            self.sums = torch.zeros(lib().nav_per_sums_count(self.capacity), dtype=torch.int64,
+                                    device=dev)
+            self.stat = torch.zeros(4, dtype=torch.int32, device=dev)
+            lib().nav_per_init(self.per_ref(), stream_handle())
 
     def desc(self):
         return NavReplay(self.rows.data_ptr(), self.capacity)
+
+    def per_desc(self):
+        return NavPer(self.pri.data_ptr(), self.sums.data_ptr(), self.stat.data_ptr(),
+                      self.capacity)
+
+    def per_ref(self):
+        """byref of the (cached) nav_per descriptor"""
+        if self._per is None:
+            d = self.per_desc()
+            self._per = (d, C.byref(d))
+        return self._per[1]
+
+    def stamp(self, base, n, stream=None):
+        """The rows a tick just pushed at `base` get the running maximum priority (on the
+        tick's stream, by advance()'s caller); nothing without priorities."""
+        if self.pri is not None:
+            lib().nav_per_stamp(self.per_ref(), int(base), int(n), stream_handle(stream))
 
     def advance(self, n):
         base = self.position
@@ -223,6 +251,7 @@ class VecEnv:
                     base, C.byref(self.out), ptr(self.demo_xy), ptr(off), epg,
                     ptr(ix.cell_start), ptr(ix.cand), ptr(reward_out), s)
             replay.advance(self.n)
+            replay.stamp(base, self.n, stream)
             return base
         has_demo = self.demo_xy is not None and self.demo_xy.shape[0] > 0
         with prof.region("agent_step", float(prof.AGENT_STEP_BYTES * self.n)):
@@ -232,6 +261,7 @@ class VecEnv:
         if has_demo:
             self.demo_reward(replay, base, reward_out=reward_out, stream=stream)
         replay.advance(self.n)
+        replay.stamp(base, self.n, stream)
         return base
 
     # the two-launch tick's second launch: the demo-proximity term (robot.py:749-757) of the envs
@@ -279,6 +309,7 @@ class VecEnv:
                 ptr(ix.cell_start) if ix else None, ptr(ix.cand) if ix else None,
                 ptr(action_out), ptr(reward_out), stream_handle(stream))
         replay.advance(self.n)
+        replay.stamp(base, self.n, stream)
         return base
 
     # robot-learning.py:78, 104-117 for every env: one greedy test episode per env in ONE launch

@@ -7,7 +7,8 @@ python tools/evaluate.py --n-envs 4096 --train-steps 0 --bc-pretrain 500 --bc-lr
 
 --bc-pretrain N first clones the demonstrations into the actor (VecTrainer.pretrain_bc: the
 reference README's baseline policy by imitation) and adds the BC loss over all demonstration rows
-before and after to the line; --bc-weight / --demo-fraction train with the demonstrations mixed in.
+before and after to the line; --bc-weight / --demo-fraction train with the demonstrations mixed in;
+--per-alpha / --per-beta / --per-eps train with prioritised replay (not together with those two).
 """
 import argparse
 import json
@@ -36,6 +37,12 @@ def main():
     ap.add_argument("--bc-lr", type=float, default=None, help="the actor's lr while pretraining")
     ap.add_argument("--bc-weight", type=float, default=0.0)
     ap.add_argument("--demo-fraction", type=float, default=0.0)
+    ap.add_argument("--per-alpha", type=float, default=0.0,
+                    help="prioritised replay: priority exponent (0 = off)")
+    ap.add_argument("--per-beta", type=float, default=0.4,
+                    help="prioritised replay: importance-weight exponent")
+    ap.add_argument("--per-eps", type=float, default=1e-6,
+                    help="prioritised replay: added to |TD error| before the exponent")
     args = ap.parse_args()
     import torch
     from nav._lib import require_gpu
@@ -47,7 +54,8 @@ def main():
         tr = VecTrainer(n_envs=args.n_envs, hidden=args.hidden, n_hidden=args.n_hidden,
                         batch=args.batch or max(args.n_envs // 2, 1), seed=args.seed,
                         envs_per_group=min(1024, args.n_envs), demos=not args.no_demos,
-                        bc_weight=args.bc_weight, demo_fraction=args.demo_fraction)
+                        bc_weight=args.bc_weight, demo_fraction=args.demo_fraction,
+                        per_alpha=args.per_alpha, per_beta=args.per_beta, per_eps=args.per_eps)
     bc = {}
     if args.bc_pretrain > 0:
         bc["bc_loss_before"] = tr.bc_loss(frame=1)
