@@ -27,8 +27,8 @@ three in a row. Nothing of it runs unless called.
 
 Learning from the demonstrations per member: a member's overrides may carry demo_fraction,
 bc_weight and q_weight (TD3Config). Then every member's ring has a tail with the frame-0
-transitions of its own env groups' demonstrations; learner="members" runs each TD3._update_bc on
-its tailed ring, learner="batched" issues one nav_td3_mix_idx_pop per epoch and
+transitions of its own env groups' demonstrations; learner="members" runs each TD3's one
+epoch loop on its tailed ring, learner="batched" issues one nav_td3_mix_idx_pop per epoch and
 nav_td3_actor_rows_bc_pop in place of nav_td3_actor_rows_pop, from a second device table of the
 members' B_demo, tail sizes and weights. With the keys in no member's overrides nothing changes.
 """
@@ -42,11 +42,11 @@ import torch
 from . import config as K
 from ._lib import (NavMlp, NavParams, NavPopScore, NavReplay, NavTd3Member, NavTd3MemberBc,
                    NavTestOut, lib, params_struct, ptr, stream_handle)
-from .cem import cem_group_demo_sets
 from .demo_replay import DemoReplay
 from .fields import make_field_device
 from .td3 import TD3
-from .vec_env import ReplayRing, VecEnv
+from .trainer import episode_summary, make_env
+from .vec_env import ReplayRing
 
 PARAM_KEYS = frozenset(name for name, _ in NavParams._fields_)
 # the learner's hyper-parameters a member may override (the batch size, the epoch count and the
@@ -204,7 +204,7 @@ class PopulationLearner:
     rebuild() after changing a member's hyper-parameter (cfg or an optimizer's lr) or replacing
     one of its buffers. If some member learns from demonstrations (TD3.bc_on), rebuild() also
     builds the BC table from the members' b_demo(), ring tails and weights, and update() runs
-    TD3._update_bc's schedule for all members (mix_launches counts its mix launches, each
+    TD3._update's demonstration steps for all members (mix_launches counts its mix launches, each
     member's _last_b_demo / bc_part serve its actor_loss_value() / bc_loss_value())."""
 
     def __init__(self, td3, rings, stream=None):
@@ -353,22 +353,24 @@ class PopulationLearner:
 
     def _step(self, group, soft_update, s):
         """The group's weight gradients, then reduce + Adam (+ the soft updates) and the packed
-        images: every member's optimizer advances as _Adam.advance() does."""
+        images: every member's optimizer counts the step, the bias corrections (equal for all,
+        _check_schedule) are the first one's (_Adam.bias_corrections)."""
         L = lib()
         L.nav_mlp_wgrad_pop(self.members, self.P, self.B, ptr(self.table), group,
                             self.wgrad_splits[group], s)
-        for t in self.td3:
-            for o in (self._opts(t)[:2] if group == 0 else self._opts(t)[2:]):
-                o.step_count += 1
-        o = self._opts(self.td3[0])[0 if group == 0 else 2]
-        bc1 = 1 - o.b1 ** o.step_count
-        bc2 = 1 - o.b2 ** o.step_count
+        o, *rest = [o for t in self.td3
+                    for o in (self._opts(t)[:2] if group == 0 else self._opts(t)[2:])]
+        for r in rest:
+            r.step_count += 1
+        bc1, bc2_sqrt = o.bias_corrections()
         L.nav_grad_reduce_adam_pop(self.members, self.P, self.B, ptr(self.table), group, o.b1,
-                                   o.b2, o.eps, bc1, math.sqrt(bc2), int(soft_update), s)
+                                   o.b2, o.eps, bc1, bc2_sqrt, int(soft_update), s)
 
     def update(self, num_epochs=None, stream=None):
-        """TD3._update's schedule for every member at once: the critic phase every epoch, the
-        actor phase with the three soft updates on epoch % policy_update_delay == 0."""
+        """TD3._update's epoch loop for every member at once, step for step: the policy-epoch
+        test, the epoch's indices (with demonstrations one mix launch, the actor's on policy
+        epochs only; injected ones come from the table), the critic rows and their step, then on
+        a policy epoch the actor rows, plain or BC, and their step with the soft updates."""
         t0 = self.td3[0]
         n = t0.cfg.num_epochs if num_epochs is None else num_epochs
         size = len(self.rings[0])
@@ -376,14 +378,13 @@ class PopulationLearner:
             raise ValueError("PopulationLearner: the rings must be filled alike")
         if size < 1:
             return
-        L, s, tab = lib(), stream_handle(stream), ptr(self.table)
+        c, L = t0.cfg, lib()
         bc = self.bc_members
+        s, tab = stream_handle(stream), ptr(self.table)
         for epoch in range(n):
+            policy = epoch % c.policy_update_delay == 0
             ctr = t0.update_counter
-            policy = epoch % t0.cfg.policy_update_delay == 0
             if bc is not None and self._mix:
-                # TD3._update_bc's order: the epoch's mixed indices (the actor's on policy epochs
-                # only), the unchanged critic launch, then the BC form of the actor launch
                 self.mix_launches += 1
                 L.nav_td3_mix_idx_pop(self.members, bc, self.P, self.B, ptr(self.bc_table), size,
                                       ctr, int(policy), s)
@@ -448,19 +449,8 @@ class PopulationTrainer:
             field = make_field_device(self.seed, self.device)
         self.field = field
         epg = int(envs_per_group) if envs_per_group else self.epm
-        self.env = VecEnv(self.n, field, seed=self.seed, envs_per_group=epg, demo_flag=demos,
-                          device=self.device)
-        if demos:  # as VecTrainer: each group's demonstrations from the batched CEM
-            G = (self.n + epg - 1) // epg
-            firsts = torch.arange(G, device=self.device) * epg
-            # (the CEM's states, actions and goals are kept for the members' DemoReplay)
-            pts, off, *self._cem = cem_group_demo_sets(
-                self.field, self.env.region[firsts].cpu().numpy(),
-                self.env.goal[firsts].cpu().numpy(), self.seed, device=self.device,
-                with_transitions=True)
-            self.env.set_demo(pts, off if G > 1 else None)
-        else:
-            self._cem = None
+        # (the CEM's states, actions and goals are kept for the members' DemoReplay)
+        self.env, self._cem = make_env(self.n, field, self.seed, epg, demos, self.device)
         lo, hi = self.seed & 0xFFFFFFFF, (self.seed >> 32) & 0xFFFFFFFF
         self.params = [params_struct(seed_lo=lo, seed_hi=hi, **pk) for pk, _, _ in routed]
         cap = int(replay_capacity or max(4 * self.epm, 2 * int(batch), K.BUFFER_SIZE))
@@ -597,17 +587,8 @@ class PopulationTrainer:
         res = []
         for m in range(self.P):
             sl = self.member_slice(m)
-            reached = out["reached"][sl].bool()
-            n_reached = int(reached.sum().item())
-            best = out["best_distance"][sl]
-            d = {"n": self.epm,
-                 "success_rate": out["reached"][sl].float().mean().item(),
-                 "mean_steps_reached": (out["steps"][sl][reached].double().mean().item()
-                                        if n_reached else float("nan")),
-                 "mean_best_distance": best.mean().item(),
-                 "max_best_distance": best.max().item(),
-                 "max_steps": int(max_steps),
-                 "episode": int(episode)}
+            d = episode_summary(out["reached"][sl], out["steps"][sl], out["best_distance"][sl],
+                                max_steps, episode)
             d.update(self.members[m])
             res.append(d)
         return res

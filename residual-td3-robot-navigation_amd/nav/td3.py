@@ -6,6 +6,7 @@ provides the stream. Sampling: robot.py:98-115 draws `batch_size` rows without r
 <=10 000-row buffer; here rows are drawn with replacement by Philox (NAV_TAG_SAMPLE) from the
 device ring, or taken from an injected index tensor (parity tests, the N=1 drop-in).
 """
+import collections
 import ctypes as C
 import math
 
@@ -15,6 +16,11 @@ from . import config as K
 from . import prof
 from ._lib import NavReplay, descs, lib, parr, ptr, stream_handle
 from .mlp import DeviceMLP
+
+# the constant arguments of nav_td3_actor_rows and nav_td3_actor_rows_bc, by the ABI's names
+_ActorRows = collections.namedtuple(
+    "_ActorRows", "actor critic batch q da bc_part acts save_mask dz dz_save_mask masks_actor "
+                  "masks_critic edge_slabs")
 
 
 class _Adam:
@@ -26,12 +32,17 @@ class _Adam:
         self.v = torch.zeros_like(net.params)
         self.step_count = 0
 
-    def advance(self):
-        """Next step's (step_size, bc2_sqrt) = (lr / (1 - b1^t), sqrt(1 - b2^t))."""
+    def bias_corrections(self):
+        """Count the next step t: its (1 - b1^t, sqrt(1 - b2^t))."""
         self.step_count += 1
         bc1 = 1 - self.b1 ** self.step_count
         bc2 = 1 - self.b2 ** self.step_count
-        return self.lr / bc1, math.sqrt(bc2)
+        return bc1, math.sqrt(bc2)
+
+    def advance(self):
+        """Next step's (step_size, bc2_sqrt) = (lr / (1 - b1^t), sqrt(1 - b2^t))."""
+        bc1, bc2_sqrt = self.bias_corrections()
+        return self.lr / bc1, bc2_sqrt
 
     def step(self, grad, stream=None):
         ss, bc2s = self.advance()
@@ -214,6 +225,11 @@ class TD3:
         h, nh = c1.hidden, c1.n_hidden
         fwd, bwd = prof.mlp_fwd_flops, prof.mlp_bwd_flops
         poly = (descs(self.target_actor), descs(t1, t2), descs(c1, c2), 2, c.tau)
+        ar = _ActorRows(actor=C.byref(ca), critic=C.byref(c1d), batch=ptr(self.batch2),
+                        q=ptr(self.q1), da=ptr(self.da), bc_part=ptr(self.bc_part),
+                        acts=ptr(self.acts_a), save_mask=mida, dz=ptr(self.dz_a),
+                        dz_save_mask=mida, masks_actor=ptr(self.mask_a),
+                        masks_critic=ptr(self.mask1), edge_slabs=ptr(self.eslab_a))
         st = {
             "keep": (ta, ca, c1d),
             "seed": (self.seed & 0xFFFFFFFF, (self.seed >> 32) & 0xFFFFFFFF),
@@ -227,10 +243,9 @@ class TD3:
                         self.split_twins),
             "ar_work": (fwd(2, 2, h, nh, B) + fwd(4, 1, h, nh, B) + bwd(4, 1, h, nh, B, True) +
                         bwd(2, 2, h, nh, B, False, True, True)),
-            "ar_head": (C.byref(ca), C.byref(c1d)),
-            "ar_tail": (ptr(self.batch2), ptr(self.q1), ptr(self.da), ptr(self.acts_a), mida,
-                        ptr(self.dz_a), mida, ptr(self.mask_a), ptr(self.mask1),
-                        ptr(self.eslab_a)),
+            "ar": ar,  # and the critic-free BC form's (pretrain_bc)
+            "ar_bc_alone": ar._replace(critic=None, q=None, masks_critic=None),
+            "td_abs": parr(self.td_abs1, self.td_abs2) if self.per_on() else None,
             "c": self._group([c1, c2], (self.critic_optimizer_1, self.critic_optimizer_2),
                              self.batch, [self.acts1, self.acts2], [self.dz1, self.dz2],
                              [self.dq1, self.dq2], 1, [self.mask1, self.mask2],
@@ -313,24 +328,18 @@ class TD3:
             self._run("grad_reduce", work, lib().nav_grad_reduce_adam, *args, ss, bc, s)
 
     # robot.py:312-366
-    def _critic_rows(self, replay, idx, eps, s):
+    def _critic_rows(self, replay, idx, eps, s, w=None):
         # sample + target actor with smoothing noise + twin target critics + TD target + online
         # twin forward with the MSE gradient + each online critic's row backward: one launch,
-        # rows in LDS throughout
+        # rows in LDS throughout. With w (prioritised replay) the weighted form: dq and the loss
+        # carry w, the twins' |TD errors| go to td_abs1 / td_abs2
         st = self._static()
-        self._run("critic_rows", st["cr_work"], lib().nav_td3_critic_rows, *st["cr_head"],
-                  self._replay_ref(replay), len(replay), self._B, ptr(idx), *st["seed"],
-                  self.update_counter, ptr(eps), *st["cr_tail"], s)
-        return st["c"]
-
-    def _critic_rows_w(self, replay, idx, eps, w, s):
-        # the weighted form of _critic_rows (prioritised replay): dq and the loss carry w, the
-        # twins' |TD errors| go to td_abs1 / td_abs2
-        st = self._static()
-        self._run("critic_rows_w", st["cr_work"], lib().nav_td3_critic_rows_w, *st["cr_head"],
-                  self._replay_ref(replay), len(replay), self._B, ptr(idx), *st["seed"],
-                  self.update_counter, ptr(eps), *st["cr_tail"], ptr(w),
-                  parr(self.td_abs1, self.td_abs2), s)
+        name, fn, tail = "critic_rows", lib().nav_td3_critic_rows, st["cr_tail"]
+        if w is not None:
+            name, fn = "critic_rows_w", lib().nav_td3_critic_rows_w
+            tail += (ptr(w), st["td_abs"])
+        self._run(name, st["cr_work"], fn, *st["cr_head"], self._replay_ref(replay), len(replay),
+                  self._B, ptr(idx), *st["seed"], self.update_counter, ptr(eps), *tail, s)
         return st["c"]
 
     def train_critic(self, replay, idx=None, eps=None, stream=None):
@@ -358,14 +367,39 @@ class TD3:
         return t[0].item(), t[1].item()
 
     # robot.py:369-398
-    def _actor_rows(self, replay, idx, s):
+    @staticmethod
+    def _actor_rows_call(a, sample, bc):
+        """(region, entry point, its arguments before the stream) from `a` (_ActorRows), `sample`
+        = (replay, size, B, idx, seed_lo, seed_hi, counter) and `bc` = None (the plain form) or
+        (B_demo, q_weight, bc_weight): each entry point's argument order, written once."""
+        if bc is None:
+            return "actor_rows", lib().nav_td3_actor_rows, (
+                a.actor, a.critic, *sample, a.batch, a.q, a.da, a.acts, a.save_mask, a.dz,
+                a.dz_save_mask, a.masks_actor, a.masks_critic, a.edge_slabs)
+        return "actor_rows_bc", lib().nav_td3_actor_rows_bc, (
+            a.actor, a.critic, *sample, *bc, a.batch, a.q, a.da, a.bc_part, a.acts, a.save_mask,
+            a.dz, a.dz_save_mask, a.masks_actor, a.masks_critic, a.edge_slabs)
+
+    def _actor_rows(self, replay, idx, s, bc=None, critic=True, ref=None, size=None):
         # sample + actor forward + critic-1 forward + backward of -mean(Q) to the action + the
-        # actor's row backward with its edge partials: one launch
+        # actor's row backward with its edge partials: one launch. With bc = (B_demo, q_weight,
+        # bc_weight) the BC form into the same workspace (critic False: the BC term alone);
+        # ref / size: a replay descriptor and its fill in place of `replay`
         st = self._static()
-        self._run("actor_rows", st["ar_work"], lib().nav_td3_actor_rows, *st["ar_head"],
-                  self._replay_ref(replay), len(replay), self._B, ptr(idx), *st["seed"],
-                  self.update_counter, *st["ar_tail"], s)
+        if bc is not None:
+            self._last_b_demo = bc[0]
+        if ref is None:
+            ref, size = self._replay_ref(replay), len(replay)
+        name, fn, args = self._actor_rows_call(
+            st["ar"] if critic else st["ar_bc_alone"],
+            (ref, size, self._B, ptr(idx), *st["seed"], self.update_counter), bc)
+        self._run(name, st["ar_work"], fn, *args, s)
         return st["a"]
+
+    def _actor_rows_bc(self, critic, replay_ref, size, idx, b_demo, q_weight, bc_weight, s):
+        """_actor_rows' BC form on a replay descriptor (critic False: the BC term alone)."""
+        return self._actor_rows(None, idx, s, (b_demo, q_weight, bc_weight), critic, replay_ref,
+                                size)
 
     def train_actor(self, replay, idx=None, stream=None, soft_update=False):
         """robot.py:369-398; with soft_update the three soft updates of robot.py:283-285 that
@@ -400,46 +434,6 @@ class TD3:
     def per_on(self):
         return self.cfg.per_alpha != 0
 
-    def _update_per(self, replay, n, idx_fn, eps_fn, stream, track_losses):
-        """_update with prioritised replay: per epoch the ring's sum hierarchy (nav_per_sums),
-        one nav_per_sample (both batches' indices from the priorities, the critic batch's
-        importance weights), the weighted critic launch, the weight gradients, reduce and Adam as
-        ever, nav_per_update with the epoch's |TD errors|, and on a policy epoch the unchanged
-        actor launch on idx_actor (its loss unweighted). An explicit idx_fn still wins: the
-        weights are then 1 and the priorities are still updated."""
-        c, L = self.cfg, lib()
-        if getattr(replay, "pri", None) is None:
-            raise ValueError("per_alpha > 0 needs a replay ring with priorities "
-                             "(ReplayRing(priorities=True))")
-        self._static()
-        s = stream_handle(stream)
-        pd, B = replay.per_ref(), self._B
-        for epoch in range(n):
-            policy = epoch % c.policy_update_delay == 0
-            self._run("per_sums", 4.0 * len(replay), L.nav_per_sums, pd, len(replay), s)
-            if idx_fn:
-                idx_c, idx_a, w = idx_fn(), (idx_fn() if policy else None), self.w_one
-                self.per_launches += 1
-            else:
-                idx_c, idx_a, w = self.idx_c, (self.idx_a if policy else None), self.w_per
-                self._run("per_sample", 16.0 * B, L.nav_per_sample, pd, len(replay), B,
-                          *self._st["seed"], self.update_counter, float(c.per_beta), ptr(idx_c),
-                          ptr(w), ptr(idx_a), s)
-                self.per_launches += 2
-            g = self._critic_rows_w(replay, idx_c, eps_fn() if eps_fn else None, w, s)
-            self._step(g, s, stream)
-            self._run("per_update", 20.0 * B, L.nav_per_update, pd, B, ptr(idx_c),
-                      ptr(self.td_abs1), ptr(self.td_abs2), float(c.per_alpha), float(c.per_eps),
-                      s)
-            self.per_launches += 1
-            if track_losses:
-                self.critic_losses.append(sum(self.critic_loss_values()) / 2)
-            if policy:
-                self.train_actor(replay, idx=idx_a, stream=stream, soft_update=True)
-                if track_losses:
-                    self.actor_losses.append(self.actor_loss_value())
-            self.update_counter += 1
-
     # ---- learning from demonstrations
     def bc_on(self):
         return self.cfg.demo_fraction != 0 or self.cfg.bc_weight != 0
@@ -458,18 +452,6 @@ class TD3:
         self.mix_launches += 1
         self._run("mix_idx", 16.0 * self._B, lib().nav_td3_mix_idx, size, self._B, b_demo,
                   demo_base, n_demo, *self._static()["seed"], counter, ptr(idx_c), ptr(idx_a), s)
-
-    def _actor_rows_bc(self, critic, replay_ref, size, idx, b_demo, q_weight, bc_weight, s):
-        """The BC form of _actor_rows into the same workspace (critic None: the BC term alone)."""
-        st = self._static()
-        self._last_b_demo = b_demo
-        t = st["ar_tail"]
-        self._run("actor_rows_bc", st["ar_work"], lib().nav_td3_actor_rows_bc, st["ar_head"][0],
-                  st["ar_head"][1] if critic else None, replay_ref, size, self._B, ptr(idx),
-                  *st["seed"], self.update_counter, b_demo, q_weight, bc_weight, t[0],
-                  t[1] if critic else None, t[2], ptr(self.bc_part), *t[3:8],
-                  t[8] if critic else None, t[9], s)
-        return st["a"]
 
     def pretrain_bc(self, rows, epochs, batch=None, lr=None, stream=None):
         """Pure behaviour cloning of the actor on the demonstration rows `rows` [n][8] (the
@@ -518,10 +500,13 @@ class TD3:
         w = self._bc_ws
         rd = NavReplay(rows.data_ptr(), n)
         ad = a.desc()
-        L.nav_td3_actor_rows_bc(C.byref(ad), None, C.byref(rd), n, n, ptr(w["idx"]), 0, 0, 0, n,
-                                0.0, 1.0, ptr(w["batch"]), None, ptr(w["da"]), ptr(w["part"]),
-                                ptr(w["acts"]), w["mid"], ptr(w["dz"]), w["mid"], ptr(w["mask"]),
-                                None, ptr(w["es"]), stream_handle(stream))
+        args = _ActorRows(actor=C.byref(ad), critic=None, batch=ptr(w["batch"]), q=None,
+                          da=ptr(w["da"]), bc_part=ptr(w["part"]), acts=ptr(w["acts"]),
+                          save_mask=w["mid"], dz=ptr(w["dz"]), dz_save_mask=w["mid"],
+                          masks_actor=ptr(w["mask"]), masks_critic=None, edge_slabs=ptr(w["es"]))
+        _, fn, args = self._actor_rows_call(args, (C.byref(rd), n, n, ptr(w["idx"]), 0, 0, 0),
+                                            (n, 0.0, 1.0))
+        fn(*args, stream_handle(stream))
         return (w["part"].double().sum() / n).item()
 
     # robot.py:293-310
@@ -555,59 +540,68 @@ class TD3:
                 collect_ready.record(stream)
 
     def _update(self, replay, n, idx_fn, eps_fn, stream, track_losses, collect_ready):
+        """The epoch loop of every mode; the modes differ in where the indices come from. Plain:
+        the row launches draw their own. Demonstrations: one nav_td3_mix_idx (the first b_demo
+        rows of both batches from the tail behind the ring), then the BC form of the actor
+        launch. Prioritised replay: nav_per_sums, one nav_per_sample (both batches' indices, the
+        critic batch's importance weights), the weighted critic launch, nav_per_update with the
+        epoch's |TD errors|; the actor's loss stays unweighted. An explicit idx_fn wins: no mix
+        (its first b_demo indices are taken to address demonstration rows), no sample (w = 1,
+        the priorities still updated). Callbacks per epoch: idx_fn (critic batch), eps_fn, and
+        once the critic phase is issued idx_fn (actor batch)."""
         if len(replay) < 1:
             return
-        if self.bc_on():
-            return self._update_bc(replay, n, idx_fn, eps_fn, stream, track_losses,
-                                   collect_ready)
-        if self.per_on():
-            return self._update_per(replay, n, idx_fn, eps_fn, stream, track_losses)
-        for epoch in range(n):
-            if (collect_ready is not None and epoch == n - 1 and self.grad_hook is not None and
-                    epoch % self.cfg.policy_update_delay != 0):
-                self._ready = collect_ready
-            self.train_critic(replay, idx=idx_fn() if idx_fn else None,
-                              eps=eps_fn() if eps_fn else None, stream=stream)
-            if track_losses:
-                self.critic_losses.append(sum(self.critic_loss_values()) / 2)
-            if epoch % self.cfg.policy_update_delay == 0:
-                # the three soft updates ride in the actor's reduce + Adam launch
-                self.train_actor(replay, idx=idx_fn() if idx_fn else None, stream=stream,
-                                 soft_update=True)
-                if track_losses:
-                    self.actor_losses.append(self.actor_loss_value())
-            self.update_counter += 1
-
-    def _update_bc(self, replay, n, idx_fn, eps_fn, stream, track_losses, collect_ready):
-        """_update with demonstrations: per epoch one nav_td3_mix_idx (the first b_demo rows of
-        both batches from the tail behind the ring), the unchanged critic launch on idx_critic,
-        and on a policy epoch the BC form of the actor launch on idx_actor; the weight gradients,
-        reduce and Adam as ever. An explicit idx_fn still wins over the mix (its first b_demo
-        indices are then taken to address demonstration rows)."""
-        c = self.cfg
-        self._static()
-        b_demo = self.b_demo()
-        n_tail = int(replay.tail.shape[0]) if hasattr(replay, "tail") else 0
-        if b_demo and not idx_fn and n_tail < 1:
-            raise ValueError("demo_fraction > 0 needs a replay ring with a demonstration tail")
+        c, L = self.cfg, lib()
+        bc, per = self.bc_on(), self.per_on()
+        if bc:
+            b_demo = self.b_demo()
+            n_tail = int(replay.tail.shape[0]) if hasattr(replay, "tail") else 0
+            if b_demo and not idx_fn and n_tail < 1:
+                raise ValueError("demo_fraction > 0 needs a replay ring with a demonstration tail")
+        if per:
+            if getattr(replay, "pri", None) is None:
+                raise ValueError("per_alpha > 0 needs a replay ring with priorities "
+                                 "(ReplayRing(priorities=True))")
+            pd = replay.per_ref()
+        seed, B = self._static()["seed"], self._B
         s = stream_handle(stream)
         for epoch in range(n):
-            if (collect_ready is not None and epoch == n - 1 and self.grad_hook is not None and
-                    epoch % c.policy_update_delay != 0):
-                self._ready = collect_ready
             policy = epoch % c.policy_update_delay == 0
+            if (collect_ready is not None and epoch == n - 1 and self.grad_hook is not None and
+                    not policy):
+                self._ready = collect_ready
+            # the epoch's indices (None: the row launches draw them) and the critic's weights
+            idx_c = idx_a = w = None
+            if per:
+                self._run("per_sums", 4.0 * len(replay), L.nav_per_sums, pd, len(replay), s)
+                self.per_launches += 1
             if idx_fn:
-                idx_c, idx_a = idx_fn(), (idx_fn() if policy else None)
-            else:
+                idx_c, w = idx_fn(), (self.w_one if per else None)
+            elif bc:
                 idx_c, idx_a = self.idx_c, self.idx_a
                 self._mix(len(replay), b_demo, replay.capacity, n_tail, self.update_counter,
                           idx_c, idx_a if policy else None, s)
-            self.train_critic(replay, idx=idx_c, eps=eps_fn() if eps_fn else None, stream=stream)
+            elif per:
+                idx_c, idx_a, w = self.idx_c, (self.idx_a if policy else None), self.w_per
+                self._run("per_sample", 16.0 * B, L.nav_per_sample, pd, len(replay), B, *seed,
+                          self.update_counter, float(c.per_beta), ptr(idx_c), ptr(w), ptr(idx_a),
+                          s)
+                self.per_launches += 1
+            g = self._critic_rows(replay, idx_c, eps_fn() if eps_fn else None, s, w)
+            self._step(g, s, stream)
+            if per:
+                self._run("per_update", 20.0 * B, L.nav_per_update, pd, B, ptr(idx_c),
+                          ptr(self.td_abs1), ptr(self.td_abs2), float(c.per_alpha),
+                          float(c.per_eps), s)
+                self.per_launches += 1
             if track_losses:
                 self.critic_losses.append(sum(self.critic_loss_values()) / 2)
             if policy:
-                g = self._actor_rows_bc(True, self._replay_ref(replay), len(replay), idx_a,
-                                        b_demo, c.q_weight, c.bc_weight, s)
+                if idx_fn:
+                    idx_a = idx_fn()
+                g = self._actor_rows(replay, idx_a, s,
+                                     (b_demo, c.q_weight, c.bc_weight) if bc else None)
+                # the three soft updates ride in the actor's reduce + Adam launch
                 self._step(g, s, stream, soft_update=True)
                 if track_losses:
                     self.actor_losses.append(self.actor_loss_value())

@@ -24,6 +24,39 @@ from .td3 import TD3
 from .vec_env import ReplayRing, VecEnv
 
 
+def make_env(n, field, seed, envs_per_group, demos, device):
+    """The VecEnv of n envs and, with `demos`, its demo set: each group's 3 demonstrations from
+    the batched GPU CEM (environment.py:140-179) + their augmentations (robot.py:771-824), as the
+    reference's robot acquires them. -> (env, the CEM's [states, actions, goals], kept for the
+    DemoReplay; None without demos)."""
+    epg = int(envs_per_group)
+    env = VecEnv(n, field, seed=seed, envs_per_group=epg, demo_flag=demos, device=device)
+    if not demos:
+        return env, None
+    G = (n + epg - 1) // epg
+    firsts = torch.arange(G, device=device) * epg
+    pts, off, *cem = cem_group_demo_sets(field, env.region[firsts].cpu().numpy(),
+                                         env.goal[firsts].cpu().numpy(), seed, device=device,
+                                         with_transitions=True)
+    env.set_demo(pts, off if G > 1 else None)
+    return env, cem
+
+
+def episode_summary(reached, steps, best_distance, max_steps, episode):
+    """The summary of one test episode per env (test_rollout's outputs, or a member's slice of
+    them) as a plain dict."""
+    hit = reached.bool()
+    n_reached = int(hit.sum().item())
+    return {"n": int(reached.shape[0]),
+            "success_rate": reached.float().mean().item(),
+            "mean_steps_reached": (steps[hit].double().mean().item() if n_reached
+                                   else float("nan")),
+            "mean_best_distance": best_distance.mean().item(),
+            "max_best_distance": best_distance.max().item(),
+            "max_steps": int(max_steps),
+            "episode": int(episode)}
+
+
 class VecTrainer:
     def __init__(self, n_envs=65536, hidden=256, n_hidden=2, batch=32768, updates_per_step=2,
                  replay_capacity=None, seed=K.RANDOM_SEED, envs_per_group=1024, demos=True,
@@ -44,21 +77,8 @@ class VecTrainer:
         if field is None:  # set_dynamics on the device (nav_fields_generate)
             field = make_field_device(self.seed, self.device)
         self.field = field
-        epg = int(envs_per_group) if envs_per_group else self.n
-        self.env = VecEnv(self.n, field, seed=self.seed, envs_per_group=epg, demo_flag=demos,
-                          device=self.device)
-        if demos:
-            G = (self.n + epg - 1) // epg
-            firsts = torch.arange(G, device=self.device) * epg
-            regions = self.env.region[firsts].cpu().numpy()
-            goals = self.env.goal[firsts].cpu().numpy()
-            # each group's 3 demonstrations from the batched GPU CEM (environment.py:140-179) +
-            # their augmentations (robot.py:771-824), as the reference's robot acquires them
-            pts, off, *self._cem = cem_group_demo_sets(self.field, regions, goals, self.seed,
-                                                       device=self.device, with_transitions=True)
-            self.env.set_demo(pts, off if G > 1 else None)
-        else:
-            self._cem = None  # the CEM's (states, actions, goals), kept for the DemoReplay
+        self.env, self._cem = make_env(self.n, field, self.seed, envs_per_group or self.n, demos,
+                                       self.device)
         cfg = K.TD3Config(batch_size=int(batch), num_epochs=int(updates_per_step),
                           net=K.NetConfig(hidden=hidden, n_hidden=n_hidden),
                           bc_weight=float(bc_weight), q_weight=float(q_weight),
@@ -168,17 +188,8 @@ class VecTrainer:
         ring, the step counter and the learner are untouched."""
         out = self.env.test_rollout(self.td3.actor_network, max_steps, episode=episode,
                                     start=start)
-        reached = out["reached"].bool()
-        n_reached = int(reached.sum().item())
-        mean_steps = (out["steps"][reached].double().mean().item() if n_reached
-                      else float("nan"))
-        return {"n": self.n,
-                "success_rate": out["reached"].float().mean().item(),
-                "mean_steps_reached": mean_steps,
-                "mean_best_distance": out["best_distance"].mean().item(),
-                "max_best_distance": out["best_distance"].max().item(),
-                "max_steps": int(max_steps),
-                "episode": int(episode)}
+        return episode_summary(out["reached"], out["steps"], out["best_distance"], max_steps,
+                               episode)
 
     # ---- the imitation baseline (the reference README's "baseline policy by imitation")
     def _demos(self):

@@ -3,6 +3,8 @@ place (TD3._run), inside prof.region only while a timer is active, so a timed up
 the very bits of an untimed one, and the timer must see the launches under the names and work
 counts bench.py --full reads. Smallest shapes at which the paths can part: 32 x 3 (k_wgrad with a
 saved middle layer) and 64 x 2 (k_wgrad_fact for the critics), batch 100 (a partial 32-row block).
+The same for the two other modes of the epoch loop: learning from demonstrations (a 64-row tail,
+25 demonstration rows per batch: no multiple of 32) and prioritised replay (a stamped ring).
 """
 import functools
 
@@ -14,6 +16,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 B, RING, EPOCHS = 100, 512, 4
 SHAPES = [(32, 3), (64, 2)]
+TAIL, DEMO_FRACTION, BC_WEIGHT = 64, 0.25, 0.5  # b_demo = 25
+PER_ALPHA = 0.6
 
 
 class _NoHook:
@@ -25,23 +29,32 @@ class _NoHook:
 
 
 @functools.lru_cache(maxsize=None)
-def _update(hidden, nh, timer, hook):
+def _update(hidden, nh, timer, hook, mode=None):
     """4 epochs of td3_update from the seed's initial networks on the seeded ring; timer: None,
-    "all" (KernelTimer()) or "none" (KernelTimer([]), the plain bench's).
-    -> (state, summary, td3)"""
+    "all" (KernelTimer()) or "none" (KernelTimer([]), the plain bench's); mode: None, "demo"
+    (demo_fraction 0.25, bc_weight 0.5, a seeded tail of 64 rows) or "per" (per_alpha 0.6, every
+    row stamped). -> (state, summary, td3)"""
     from nav import _lib, prof
     from nav import config as K
     from nav.td3 import TD3
     from nav.vec_env import ReplayRing
     _lib.require_gpu()
+    extra = {"demo": dict(demo_fraction=DEMO_FRACTION, bc_weight=BC_WEIGHT),
+             "per": dict(per_alpha=PER_ALPHA)}.get(mode, {})
     cfg = K.TD3Config(batch_size=B, num_epochs=EPOCHS, policy_update_delay=2,
-                      net=K.NetConfig(hidden=hidden, n_hidden=nh))
+                      net=K.NetConfig(hidden=hidden, n_hidden=nh), **extra)
     td3 = TD3(cfg, DEV, seed=4321, grad_hook=_NoHook() if hook else None)
     rng = np.random.default_rng(9)
-    ring = ReplayRing(RING, DEV)
+    ring = ReplayRing(RING, DEV, tail=TAIL if mode == "demo" else 0, priorities=mode == "per")
     ring.rows.copy_(torch.tensor(rng.uniform(-5, 5, (RING, 8)).astype(np.float32)))
     ring.rows[:, 7] = (ring.rows[:, 7] > 4.8).float()  # ~2 % dones
     ring.size = RING
+    if mode == "demo":
+        assert td3.b_demo() == 25
+        ring.tail.copy_(torch.tensor(rng.uniform(-5, 5, (TAIL, 8)).astype(np.float32)))
+        ring.tail[:, 7] = 0
+    if mode == "per":
+        ring.stamp(0, RING)
     summary = None
     if timer is None:
         td3.td3_update(ring)
@@ -51,7 +64,12 @@ def _update(hidden, nh, timer, hook):
             td3.td3_update(ring)
         summary = t.summary()
     torch.cuda.synchronize()
-    state = {"update_counter": td3.update_counter}
+    state = {"update_counter": td3.update_counter, "mix_launches": td3.mix_launches,
+             "per_launches": td3.per_launches}
+    if mode == "demo":
+        state["bc_part"] = td3.bc_part.clone()
+    if mode == "per":
+        state["pri"], state["stat"] = ring.pri.clone(), ring.stat.clone()
     for name, net in td3.networks().items():
         state[name + ".params"] = net.params.clone()
         state[name + ".packed"] = net.packed.clone()
@@ -71,7 +89,7 @@ def _assert_same(a, b):
             assert v == b[k], k
 
 
-def _expected(td3, hidden, nh, hook):
+def _expected(td3, hidden, nh, hook, mode=None):
     """The regions of 4 epochs (policy epochs 0 and 2) with their launch counts and total work:
     the formulas written out."""
     from nav._lib import lib
@@ -108,6 +126,15 @@ def _expected(td3, hidden, nh, hook):
         exp["mlp_wgrad"] = (6, 4 * 2 * wg + 2 * wg)
     if hook:  # one message per bucket: [critic 1 | critic 2] x 4, the actor's x 2
         exp["allreduce"] = (6, 4 * (2 * cc * 4.0) + 2 * (ca * 4.0))
+    if mode == "demo":  # one mix per epoch (both batches' indices), the BC form of the actor rows
+        exp["mix_idx"] = (4, 4 * 16.0 * B)
+        exp["actor_rows_bc"] = exp.pop("actor_rows")
+    if mode == "per":  # the sum hierarchy, one sample and one priority update per epoch, around
+        # the weighted form of the critic rows
+        exp["per_sums"] = (4, 4 * 4.0 * RING)
+        exp["per_sample"] = (4, 4 * 16.0 * B)
+        exp["critic_rows_w"] = exp.pop("critic_rows")
+        exp["per_update"] = (4, 4 * 20.0 * B)
     return exp
 
 
@@ -137,3 +164,24 @@ def test_timed_update_with_hook_bit_equal_and_regions(hidden, nh):
     full, summary, td3 = _update(hidden, nh, "all", True)
     _assert_same(ref, full)
     _assert_summary(summary, _expected(td3, hidden, nh, True))
+
+
+@pytest.mark.parametrize("hidden,nh", SHAPES)
+def test_timed_demo_update_bit_equal_and_regions(hidden, nh):
+    ref, _, _ = _update(hidden, nh, None, False, "demo")
+    assert ref["update_counter"] == EPOCHS and ref["actor.t"] == 2 and ref["critic1.t"] == 4
+    assert ref["mix_launches"] == 4 and ref["per_launches"] == 0
+    assert ref["bc_part"].sum().item() > 0
+    full, summary, td3 = _update(hidden, nh, "all", False, "demo")
+    _assert_same(ref, full)
+    _assert_summary(summary, _expected(td3, hidden, nh, False, "demo"))
+
+
+@pytest.mark.parametrize("hidden,nh", SHAPES)
+def test_timed_per_update_bit_equal_and_regions(hidden, nh):
+    ref, _, _ = _update(hidden, nh, None, False, "per")
+    assert ref["update_counter"] == EPOCHS and ref["actor.t"] == 2 and ref["critic1.t"] == 4
+    assert ref["per_launches"] == 12 and ref["mix_launches"] == 0
+    full, summary, td3 = _update(hidden, nh, "all", False, "per")
+    _assert_same(ref, full)
+    _assert_summary(summary, _expected(td3, hidden, nh, False, "per"))

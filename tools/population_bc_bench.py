@@ -7,7 +7,7 @@ unit is one policy epoch (mix, critic phase, BC actor phase, soft updates) plus 
 epoch (mix, critic phase):
   (batched_bc)  PopulationLearner.update: one launch per kernel for all members, one
                 nav_td3_mix_idx_pop per epoch and nav_td3_actor_rows_bc_pop on policy epochs;
-  (members_bc)  every member's td3_update (TD3._update_bc) in turn on one stream: what
+  (members_bc)  every member's td3_update (TD3._update) in turn on one stream: what
                 learner="members" does;
   (batched)     the batched learner of members without the keys on the same rings: the plain
                 epochs, for the ratio.
