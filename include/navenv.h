@@ -659,6 +659,40 @@ int nav_per_sample(const nav_per* per, int64_t size, int64_t B, uint32_t seed_lo
  * NAV_EINVAL: B < 1, NULL idx / td1 / td2, alpha <= 0 or NaN, eps < 0 or NaN. */
 int nav_per_update(const nav_per* per, int64_t B, const int64_t* idx, const float* td1,
                    const float* td2, float alpha, float eps, void* stream);
+/* ---- Multi-step returns: n-step TD targets from the replay ring ----
+ * A tick pushes env e to slot (base + e) % capacity and the ring's write position moves by n_envs
+ * per tick, so the successor of ring row k for the same env is row (k + n_envs) % capacity: the
+ * stride. Column 7 (done) marks only a path end; the tick also resets an env after a goal or a
+ * stuck step, and that lives in nav_step_out.flags bit3 alone. `cut` [capacity] u8 beside the ring
+ * keeps it: 1 where the env was reset after that row (a done row is always a cut row). */
+/* cut[(pos + i) % capacity] = (flags[i] >> 3) & 1 (nav_step_out.flags bit3 'ended'), i < n;
+ * n = 0 is a no-op. NAV_EINVAL: NULL cut / flags, capacity < 1, n < 0 or > capacity,
+ * pos outside [0, capacity). */
+int nav_nstep_stamp(uint8_t* cut, int64_t capacity, int64_t pos, int64_t n,
+                    const uint8_t* flags, void* stream);
+#define NAV_NSTEP_MAX 16
+/* The critic batch of one epoch as n-step rows. Row b: k0 = idx[b] if idx is given, else the
+ * index the row kernels draw themselves ((w.x * size) >> 32 of Philox NAV_TAG_SAMPLE at
+ * ctr = (b, 0, 4, 2*counter)). age = (position - 1 - k0) mod capacity (rows written after k0).
+ * With k_j = (k0 + j*stride) % capacity, the horizon m is the smallest j >= 1 with
+ *   j == n_step, or cut[k_{j-1}] != 0, or (j * stride) > age      (the write head).
+ * R = sum_{j<m} g^j * (double)rows[k_j][4] in double, g = (double)gamma, g^j by repeated
+ * multiplication, terms added in ascending j (starting from the j = 0 term itself); last =
+ * rows[k_{m-1}].
+ * staged[b] = { rows[k0][0..3], (float)R, last[5], last[6],
+ *               last[7] != 0 ? 1.0f : (float)(1.0 - g^{m-1}) };  steps[b] (nullable) = m.
+ * For m == 1 the staged row equals rows[k0] bit for bit. Through nav_td3_critic_rows (or _w) with
+ * replay = (staged, capacity B), size = B and idx = 0 .. B-1 the target is the n-step one,
+ * y = R + (gamma * min Q'(s_{t+m}, a')) * (1.0f - staged[7]): the effective discount
+ * gamma * fl32(1.0f - staged[7]) is exact for m == 1 and within one f32 rounding of gamma^m for
+ * m > 1 (0 after a done row).
+ * NAV_EINVAL: NULL replay / rows / cut / staged, size < 1 or > capacity, position outside
+ * [0, capacity), position != size while size < capacity, stride < 1, n_step < 1 or
+ * > NAV_NSTEP_MAX, B < 1, gamma outside [0, 1] or NaN. idx values must lie in [0, size). */
+int nav_nstep_rows(const nav_replay* replay, const uint8_t* cut, int64_t size, int64_t position,
+                   int64_t stride, int32_t n_step, float gamma, int64_t B, const int64_t* idx,
+                   uint32_t seed_lo, uint32_t seed_hi, uint32_t counter, float* staged,
+                   int32_t* steps, void* stream);
 /* Fill / strided copy helpers of the TD3 glue (robot.py:329-339, 386-390). */
 int nav_fill(float* x, int64_t n, float value, void* stream);
 int nav_strided_copy(const float* src, int32_t ld_src, int32_t col_src, float* dst, int32_t ld_dst,

@@ -50,6 +50,9 @@ TD3_BATCH_SIZE = 100
 GAMMA = 0.99
 TAU = 0.001
 
+# include/navenv.h
+NSTEP_MAX = 16  # NAV_NSTEP_MAX: the longest multi-step return
+
 
 @dataclass
 class NetConfig:
@@ -87,4 +90,22 @@ class TD3Config:
     per_alpha: float = 0.0
     per_beta: float = 0.4
     per_eps: float = 1e-6
+    # multi-step returns (off by default, n_step == 1): the critics' target is
+    # r_t + ... + gamma^(k-1) r_{t+k-1} + gamma^k min Q'(s_{t+k}, a') with k <= n_step, cut short
+    # where the env was reset or the ring's write head is reached (1 .. NAV_NSTEP_MAX = 16)
+    n_step: int = 1
     net: NetConfig = field(default_factory=NetConfig)
+
+    def check_n_step(self, grad_hook=None):
+        """ValueError for an n_step outside 1 .. NAV_NSTEP_MAX, or n_step > 1 with what
+        multi-step returns do not combine with (needs no device)."""
+        if not isinstance(self.n_step, int) or not 1 <= self.n_step <= NSTEP_MAX:
+            raise ValueError(f"n_step must be an int in 1 .. {NSTEP_MAX} (1 = multi-step "
+                             "returns off)")
+        if self.n_step > 1:
+            if self.demo_fraction != 0 or self.bc_weight != 0:
+                raise ValueError("multi-step returns (n_step > 1) do not combine with "
+                                 "demo_fraction / bc_weight")
+            if grad_hook is not None:
+                raise ValueError("multi-step returns (n_step > 1) do not combine with a "
+                                 "grad_hook (shared policy)")

@@ -431,6 +431,9 @@ class PopulationTrainer:
             if ck.get("per_alpha", 0.0) != 0:
                 raise ValueError("prioritised replay (per_alpha > 0) is not available to "
                                  f"population members: member {m}")
+            if ck.get("n_step", 1) != 1:
+                raise ValueError("multi-step returns (n_step > 1) are not available to "
+                                 f"population members: member {m}")
         # learning from the demonstrations: on for a member whose demo_fraction or bc_weight is
         # non-zero (TD3.bc_on); then every member's ring carries a tail of its own envs'
         # demonstrations

@@ -62,6 +62,10 @@ class TD3:
                  critic2=None, grad_hook=None, wgrad_splits=None):
         self.cfg = cfg or K.TD3Config()
         c = self.cfg
+        # multi-step returns (cfg.n_step > 1; off by default): what it does not combine with is
+        # refused before anything is allocated
+        self.nstep_launches = 0  # nav_nstep_rows calls issued (0 with the feature off)
+        c.check_n_step(grad_hook)
         nc = c.net
         self.device = torch.device(device)
         mk = lambda di, do: DeviceMLP(di, do, nc.hidden, nc.n_hidden, self.device)  # noqa: E731
@@ -152,6 +156,13 @@ class TD3:
         if self.per_on():
             self.w_per, self.w_one = f(B), torch.ones(B, dtype=torch.float32, device=d)
             self.td_abs1, self.td_abs2 = f(B), f(B)
+        # multi-step returns: the epoch's critic batch as n-step rows, their horizons, and the
+        # indices 0 .. B-1 the critic launch reads them by
+        if self.nstep_on():
+            self.staged = f(B, 8)
+            self.steps = torch.zeros(B, dtype=torch.int32, device=d)
+            self.idx_iota = torch.arange(B, dtype=torch.int64, device=d)
+            self._staged_rd = NavReplay(self.staged.data_ptr(), B)
         ec = L.nav_mlp_edge_count(4, 1, hp, nh)
         self.eslab1, self.eslab2 = f(self.nblk, ec), f(self.nblk, ec)
         self.eslab_a = f(self.nblk, L.nav_mlp_edge_count(2, 2, hp, nh))
@@ -214,7 +225,7 @@ class TD3:
         if B != self._B:
             self._workspace(B)
         key = (B, self.seed, c.policy_noise, c.noise_clip, c.max_action, c.gamma, c.tau,
-               self.split_twins, c.bc_weight, c.q_weight, c.demo_fraction, c.per_alpha)
+               self.split_twins, c.bc_weight, c.q_weight, c.demo_fraction, c.per_alpha, c.n_step)
         if self._st is not None and self._st_key == key:
             return self._st
         c1, c2, a = self.critic_network_1, self.critic_network_2, self.actor_network
@@ -328,19 +339,35 @@ class TD3:
             self._run("grad_reduce", work, lib().nav_grad_reduce_adam, *args, ss, bc, s)
 
     # robot.py:312-366
-    def _critic_rows(self, replay, idx, eps, s, w=None):
+    def _critic_rows(self, replay, idx, eps, s, w=None, staged=False):
         # sample + target actor with smoothing noise + twin target critics + TD target + online
         # twin forward with the MSE gradient + each online critic's row backward: one launch,
         # rows in LDS throughout. With w (prioritised replay) the weighted form: dq and the loss
-        # carry w, the twins' |TD errors| go to td_abs1 / td_abs2
+        # carry w, the twins' |TD errors| go to td_abs1 / td_abs2. staged (multi-step returns):
+        # the rows are self.staged's B rows in order, in place of `replay` and `idx`
         st = self._static()
         name, fn, tail = "critic_rows", lib().nav_td3_critic_rows, st["cr_tail"]
         if w is not None:
             name, fn = "critic_rows_w", lib().nav_td3_critic_rows_w
             tail += (ptr(w), st["td_abs"])
-        self._run(name, st["cr_work"], fn, *st["cr_head"], self._replay_ref(replay), len(replay),
-                  self._B, ptr(idx), *st["seed"], self.update_counter, ptr(eps), *tail, s)
+        if staged:
+            ref, size, idx = C.byref(self._staged_rd), self._B, self.idx_iota
+        else:
+            ref, size = self._replay_ref(replay), len(replay)
+        self._run(name, st["cr_work"], fn, *st["cr_head"], ref, size, self._B, ptr(idx),
+                  *st["seed"], self.update_counter, ptr(eps), *tail, s)
         return st["c"]
+
+    def _nstep_rows(self, replay, idx, s):
+        """The epoch's critic batch as n-step rows into self.staged (nav_nstep_rows): row b from
+        ring row idx[b], or from the index the critic launch would draw itself."""
+        c = self.cfg
+        self.nstep_launches += 1
+        self._run("nstep_rows", 32.0 * (c.n_step + 2) * self._B, lib().nav_nstep_rows,
+                  self._replay_ref(replay), ptr(replay.cut), len(replay), replay.position,
+                  int(replay.stride), c.n_step, c.gamma, self._B, ptr(idx),
+                  *self._static()["seed"], self.update_counter, ptr(self.staged),
+                  ptr(self.steps), s)
 
     def train_critic(self, replay, idx=None, eps=None, stream=None):
         s = stream_handle(stream)
@@ -433,6 +460,10 @@ class TD3:
     # ---- prioritised replay
     def per_on(self):
         return self.cfg.per_alpha != 0
+
+    # ---- multi-step returns
+    def nstep_on(self):
+        return self.cfg.n_step > 1
 
     # ---- learning from demonstrations
     def bc_on(self):
@@ -547,7 +578,11 @@ class TD3:
         critic batch's importance weights), the weighted critic launch, nav_per_update with the
         epoch's |TD errors|; the actor's loss stays unweighted. An explicit idx_fn wins: no mix
         (its first b_demo indices are taken to address demonstration rows), no sample (w = 1,
-        the priorities still updated). Callbacks per epoch: idx_fn (critic batch), eps_fn, and
+        the priorities still updated). Multi-step returns (n_step > 1) sit on top of the plain,
+        prioritised and idx_fn modes: nav_nstep_rows stages the critic batch of those indices
+        (None: the indices the launch would draw) as n-step rows, and the unchanged critic launch
+        reads the staged rows in order, with its own counter and eps; the actor launch and
+        nav_per_update keep the ring indices. Callbacks per epoch: idx_fn (critic batch), eps_fn, and
         once the critic phase is issued idx_fn (actor batch)."""
         if len(replay) < 1:
             return
@@ -563,6 +598,16 @@ class TD3:
                 raise ValueError("per_alpha > 0 needs a replay ring with priorities "
                                  "(ReplayRing(priorities=True))")
             pd = replay.per_ref()
+        nstep = self.nstep_on()
+        if nstep:
+            if getattr(replay, "cut", None) is None:
+                raise ValueError("n_step > 1 needs a replay ring with cut marks "
+                                 "(ReplayRing(cuts=True))")
+            if not getattr(replay, "stride", None):
+                raise ValueError("n_step > 1 needs the ring's stride (ReplayRing.stride: the "
+                                 "rows between an env's consecutive transitions, n_envs)")
+            if getattr(self, "staged", None) is None or self.staged.shape[0] != c.batch_size:
+                self._B = 0  # n_step switched on after the workspace was built
         seed, B = self._static()["seed"], self._B
         s = stream_handle(stream)
         for epoch in range(n):
@@ -587,7 +632,9 @@ class TD3:
                           self.update_counter, float(c.per_beta), ptr(idx_c), ptr(w), ptr(idx_a),
                           s)
                 self.per_launches += 1
-            g = self._critic_rows(replay, idx_c, eps_fn() if eps_fn else None, s, w)
+            if nstep:  # the critic batch staged as n-step rows; the launch reads them in order
+                self._nstep_rows(replay, idx_c, s)
+            g = self._critic_rows(replay, idx_c, eps_fn() if eps_fn else None, s, w, nstep)
             self._step(g, s, stream)
             if per:
                 self._run("per_update", 20.0 * B, L.nav_per_update, pd, B, ptr(idx_c),

@@ -62,7 +62,7 @@ class VecTrainer:
                  replay_capacity=None, seed=K.RANDOM_SEED, envs_per_group=1024, demos=True,
                  device="cuda", field=None, grad_hook=None, fuse_tick=True, overlap_collect=False,
                  demo_fraction=0.0, bc_weight=0.0, q_weight=1.0, demo_rows=None,
-                 per_alpha=0.0, per_beta=0.4, per_eps=1e-6):
+                 per_alpha=0.0, per_beta=0.4, per_eps=1e-6, n_step=1):
         """demo_fraction / bc_weight / q_weight: learning from the demonstrations (TD3Config; off
         by default). With demo_fraction or bc_weight non-zero the CEM demonstrations' transitions
         sit in a tail behind the replay ring and a share of every batch is drawn from it (needs
@@ -70,7 +70,18 @@ class VecTrainer:
         per_alpha / per_beta / per_eps: prioritised replay (TD3Config; off at per_alpha == 0).
         On, the ring carries one priority per row, every tick stamps its rows with the running
         maximum, and batches are drawn in proportion to priority. Not with demo_fraction /
-        bc_weight, a grad_hook or overlap_collect (ValueError)."""
+        bc_weight, a grad_hook or overlap_collect (ValueError).
+        n_step: multi-step returns (TD3Config; off at 1). On, the ring carries one cut mark per
+        row, every tick writes its rows' marks from its flags, and the critics' target sums up to
+        n_step rewards along the env's rows (stride n_envs). With per_alpha it combines; not with
+        demo_fraction / bc_weight, a grad_hook or overlap_collect (ValueError)."""
+        # multi-step returns: what they do not combine with is refused before anything is built
+        # (the gather reads rows an overlapped tick may be writing); the learner refuses the rest
+        K.TD3Config(n_step=n_step, demo_fraction=float(demo_fraction),
+                    bc_weight=float(bc_weight)).check_n_step(grad_hook)
+        if n_step > 1 and overlap_collect:
+            raise ValueError("multi-step returns (n_step > 1) do not combine with "
+                             "overlap_collect")
         self.n = int(n_envs)
         self.device = torch.device(device)
         self.seed = int(seed)
@@ -83,7 +94,7 @@ class VecTrainer:
                           net=K.NetConfig(hidden=hidden, n_hidden=n_hidden),
                           bc_weight=float(bc_weight), q_weight=float(q_weight),
                           demo_fraction=float(demo_fraction), per_alpha=float(per_alpha),
-                          per_beta=float(per_beta), per_eps=float(per_eps))
+                          per_beta=float(per_beta), per_eps=float(per_eps), n_step=n_step)
         if cfg.per_alpha != 0 and overlap_collect:
             raise ValueError("prioritised replay (per_alpha > 0) does not combine with "
                              "overlap_collect")
@@ -104,10 +115,12 @@ class VecTrainer:
             else:
                 raise ValueError("demo_fraction / bc_weight need demonstrations: demos=True")
         else:
-            self.replay = ReplayRing(cap, self.device, priorities=self.td3.per_on())
+            self.replay = ReplayRing(cap, self.device, priorities=self.td3.per_on(),
+                                     cuts=self.td3.nstep_on())
             if demo_rows is not None:
                 self.demo_replay = DemoReplay.from_rows(demo_rows[0].to(self.device),
                                                         demo_rows[1])
+        self.replay.stride = self.n  # an env's next transition: n_envs rows on
         self.action = torch.zeros(self.n, 2, dtype=torch.float64, device=self.device)
         self.steps = 0
         self.updates_per_step = int(updates_per_step)
@@ -244,6 +257,9 @@ class VecTrainer:
             c = self.td3.cfg
             sd["meta"].update(per_alpha=c.per_alpha, per_beta=c.per_beta, per_eps=c.per_eps)
             sd["replay"].update(pri=self.replay.pri.cpu(), stat=self.replay.stat.cpu())
+        if self.td3.nstep_on():  # multi-step returns: the horizon and the cut marks
+            sd["meta"].update(n_step=self.td3.cfg.n_step)
+            sd["replay"].update(cut=self.replay.cut.cpu())
         return sd
 
     def load_state_dict(self, sd):
@@ -262,6 +278,8 @@ class VecTrainer:
             self.replay.pri.copy_(sd["replay"]["pri"].to(self.device))
             self.replay.stat.copy_(sd["replay"]["stat"].to(self.device))
             self.td3.cfg.per_beta = float(m["per_beta"])
+        if self.td3.nstep_on():
+            self.replay.cut.copy_(sd["replay"]["cut"].to(self.device))
         self.td3.load_state_dict(sd["td3"])
         self.steps = int(m["steps"])
         self.updates_per_step = int(m["updates_per_step"])
@@ -282,7 +300,7 @@ class VecTrainer:
                 q_weight=m.get("q_weight", 1.0),
                 demo_rows=None if dr is None else (dr["rows0"], dr["rows1"]),
                 per_alpha=m.get("per_alpha", 0.0), per_beta=m.get("per_beta", 0.4),
-                per_eps=m.get("per_eps", 1e-6))
+                per_eps=m.get("per_eps", 1e-6), n_step=int(m.get("n_step", 1)))
         t.load_state_dict(sd)
         return t
 

@@ -75,7 +75,7 @@ class ReplayRing:
     """ReplayBuffer (robot.py:58-124) as a device ring of 32-byte rows
     (s0 s1 a0 a1 r s'0 s'1 done, float32)."""
 
-    def __init__(self, capacity, device="cuda", rows=None, tail=0, priorities=False):
+    def __init__(self, capacity, device="cuda", rows=None, tail=0, priorities=False, cuts=False):
         self.capacity = int(capacity)
         n_tail = int(tail)
         if rows is None:
@@ -106,6 +106,13 @@ class ReplayRing:
                                     device=dev)
             self.stat = torch.zeros(4, dtype=torch.int32, device=dev)
             lib().nav_per_init(self.per_ref(), stream_handle())
+        # multi-step returns: one u8 cut mark per ring row, 1 where the env was reset after that
+        # row (nav_nstep_stamp), and the row distance between an env's consecutive transitions
+        # (the trainer's n_envs; set by the trainer); none without `cuts`
+        self.cut = None
+        self.stride = None
+        if cuts:
+            self.cut = torch.zeros(self.capacity, dtype=torch.uint8, device=self.rows.device)
 
     def desc(self):
         return NavReplay(self.rows.data_ptr(), self.capacity)
@@ -121,11 +128,15 @@ class ReplayRing:
             self._per = (d, C.byref(d))
         return self._per[1]
 
-    def stamp(self, base, n, stream=None):
+    def stamp(self, base, n, stream=None, flags=None):
         """The rows a tick just pushed at `base` get the running maximum priority (on the
-        tick's stream, by advance()'s caller); nothing without priorities."""
+        tick's stream, by advance()'s caller); nothing without priorities. With cut marks and
+        the tick's `flags` [n] u8, the rows' marks become the flags' bit 3 ('ended')."""
         if self.pri is not None:
             lib().nav_per_stamp(self.per_ref(), int(base), int(n), stream_handle(stream))
+        if self.cut is not None and flags is not None:
+            lib().nav_nstep_stamp(ptr(self.cut), self.capacity, int(base), int(n), ptr(flags),
+                                  stream_handle(stream))
 
     def advance(self, n):
         base = self.position
@@ -251,7 +262,7 @@ class VecEnv:
                     base, C.byref(self.out), ptr(self.demo_xy), ptr(off), epg,
                     ptr(ix.cell_start), ptr(ix.cand), ptr(reward_out), s)
             replay.advance(self.n)
-            replay.stamp(base, self.n, stream)
+            replay.stamp(base, self.n, stream, self.flags)
             return base
         has_demo = self.demo_xy is not None and self.demo_xy.shape[0] > 0
         with prof.region("agent_step", float(prof.AGENT_STEP_BYTES * self.n)):
@@ -261,7 +272,7 @@ class VecEnv:
         if has_demo:
             self.demo_reward(replay, base, reward_out=reward_out, stream=stream)
         replay.advance(self.n)
-        replay.stamp(base, self.n, stream)
+        replay.stamp(base, self.n, stream, self.flags)
         return base
 
     # the two-launch tick's second launch: the demo-proximity term (robot.py:749-757) of the envs
@@ -309,7 +320,7 @@ class VecEnv:
                 ptr(ix.cell_start) if ix else None, ptr(ix.cand) if ix else None,
                 ptr(action_out), ptr(reward_out), stream_handle(stream))
         replay.advance(self.n)
-        replay.stamp(base, self.n, stream)
+        replay.stamp(base, self.n, stream, self.flags)
         return base
 
     # robot-learning.py:78, 104-117 for every env: one greedy test episode per env in ONE launch

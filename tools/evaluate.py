@@ -8,7 +8,8 @@ python tools/evaluate.py --n-envs 4096 --train-steps 0 --bc-pretrain 500 --bc-lr
 --bc-pretrain N first clones the demonstrations into the actor (VecTrainer.pretrain_bc: the
 reference README's baseline policy by imitation) and adds the BC loss over all demonstration rows
 before and after to the line; --bc-weight / --demo-fraction train with the demonstrations mixed in;
---per-alpha / --per-beta / --per-eps train with prioritised replay (not together with those two).
+--per-alpha / --per-beta / --per-eps train with prioritised replay (not together with those two);
+--n-step N trains on N-step returns (with prioritised replay or alone, not with those two).
 """
 import argparse
 import json
@@ -43,6 +44,8 @@ def main():
                     help="prioritised replay: importance-weight exponent")
     ap.add_argument("--per-eps", type=float, default=1e-6,
                     help="prioritised replay: added to |TD error| before the exponent")
+    ap.add_argument("--n-step", type=int, default=1,
+                    help="multi-step returns: the longest horizon (1 = off, at most 16)")
     args = ap.parse_args()
     import torch
     from nav._lib import require_gpu
@@ -55,7 +58,8 @@ def main():
                         batch=args.batch or max(args.n_envs // 2, 1), seed=args.seed,
                         envs_per_group=min(1024, args.n_envs), demos=not args.no_demos,
                         bc_weight=args.bc_weight, demo_fraction=args.demo_fraction,
-                        per_alpha=args.per_alpha, per_beta=args.per_beta, per_eps=args.per_eps)
+                        per_alpha=args.per_alpha, per_beta=args.per_beta, per_eps=args.per_eps,
+                        n_step=args.n_step)
     bc = {}
     if args.bc_pretrain > 0:
         bc["bc_loss_before"] = tr.bc_loss(frame=1)
@@ -67,6 +71,8 @@ def main():
     res = tr.evaluate(max_steps=args.max_steps, episode=args.episode)
     torch.cuda.synchronize()
     res["train_steps"] = tr.steps
+    if tr.td3.nstep_on():
+        res["n_step"] = tr.td3.cfg.n_step
     res.update(bc)
     # strict JSON: a NaN (no env reached) prints as null
     print(json.dumps({k: None if isinstance(v, float) and v != v else v for k, v in res.items()}))
