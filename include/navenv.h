@@ -482,6 +482,29 @@ int nav_td3_actor_rows_bc(const nav_mlp* actor, const nav_mlp* critic, const nav
                           float* acts, uint32_t save_mask, float* dz, uint32_t dz_save_mask,
                           uint16_t* masks_actor, uint16_t* masks_critic, float* edge_slabs,
                           void* stream);
+/* nav_td3_actor_rows_bc (with a critic) with the Q-filter of Nair et al. 2018 on its BC term: a
+ * demonstration row adds its term only where the critic rates the demonstrated action above the
+ * policy's own,
+ *   L = -q_weight * mean_{b<B} Q1(s_b, pi(s_b))
+ *       + bc_weight * (1/B_demo) * sum_{b<B_demo, keep_b} sum_j (pi_j(s_b) - a_{b,j})^2
+ *   keep_b = Q1(s_b, a_b) > Q1(s_b, pi(s_b))   (strict; a NaN compares false: dropped)
+ * Q1(s_b, pi(s_b)) is the value written to q[b]; Q1(s_b, a_b) is the same critic, the same weight
+ * images, in the same launch, on the sampled row's own action columns: one more critic forward
+ * in the workgroups that hold demonstration rows (the batch's prefix). The normaliser stays
+ * B_demo, not the number of kept rows, so (float)(2*bc_weight/B_demo) stays a launch constant and
+ * no count crosses the workgroups before the backward pass. The decision carries no gradient.
+ * q_demo [B] (nullable): Q1(s_b, a_b) of rows b < B_demo; rows >= B_demo are not written.
+ * bc_part [row blocks]: each block's sum over its kept rows, in nav_td3_actor_rows_bc's order.
+ * keep_part [row blocks]: the block's kept demonstration rows (rows, not row components).
+ * With B_demo == 0 every output equals nav_td3_actor_rows_bc's bit for bit, keep_part all 0.
+ * NAV_EINVAL: what nav_td3_actor_rows_bc refuses, critic NULL, keep_part NULL, q NULL. */
+int nav_td3_actor_rows_bcq(const nav_mlp* actor, const nav_mlp* critic, const nav_replay* replay,
+                           int64_t size, int64_t B, const int64_t* idx, uint32_t seed_lo,
+                           uint32_t seed_hi, uint32_t counter, int64_t B_demo, float q_weight,
+                           float bc_weight, float* batch, float* q, float* da, float* bc_part,
+                           float* q_demo, int32_t* keep_part, float* acts, uint32_t save_mask,
+                           float* dz, uint32_t dz_save_mask, uint16_t* masks_actor,
+                           uint16_t* masks_critic, float* edge_slabs, void* stream);
 /* u16 words of the ReLU mask image for M rows (layout: [n_hidden][row tiles][hp/32][64]). */
 int64_t nav_mlp_mask_count(int32_t hidden_pad, int32_t n_hidden, int64_t M);
 /* Parameter gradients are produced in two parts that nav_grad_reduce combines:

@@ -4,7 +4,7 @@
 #include "mlp_rows_role.h"
 #include "pop_host.h"
 
-// the 6 x 8 launcher objects' dispatchers
+// the 7 x 8 launcher objects' dispatchers
 #define NAV_ROWS_DECL(role, nt) rows_fn NAV_ROWS_FN(role, nt);
 #define NAV_ROWS_DECL_ROLE(role) NAV_ROWS_NTS(NAV_ROWS_DECL, role)
 NAV_ROWS_ROLES(NAV_ROWS_DECL_ROLE)
@@ -655,6 +655,32 @@ int nav_td3_actor_rows_bc(const nav_mlp* actor, const nav_mlp* critic, const nav
     x.bc.bc_coef = B_demo > 0 ? (float)(2.0 * (double)bc_weight / (double)B_demo) : 0.f;
     x.bc.bc_part = bc_part;
     return rows_dispatch(x.r.actor.hp, FAM_ACTOR_BC, 0, 0, &x, 1, x.r.B, S(stream));
+}
+
+int nav_td3_actor_rows_bcq(const nav_mlp* actor, const nav_mlp* critic, const nav_replay* replay,
+                           int64_t size, int64_t B, const int64_t* idx, uint32_t seed_lo,
+                           uint32_t seed_hi, uint32_t counter, int64_t B_demo, float q_weight,
+                           float bc_weight, float* batch, float* q, float* da, float* bc_part,
+                           float* q_demo, int32_t* keep_part, float* acts, uint32_t save_mask,
+                           float* dz, uint32_t dz_save_mask, uint16_t* masks_actor,
+                           uint16_t* masks_critic, float* edge_slabs, void* stream) {
+    ActorRowsBcqArgs x{};
+    // the BC form's refusals, and the filter's own: it compares critic 1's values
+    if (B_demo < 0 || B_demo > B || (bc_weight != 0.f && B_demo == 0) || !bc_part || !critic ||
+        !keep_part || !q)
+        return NAV_EINVAL;
+    ActorRowsArgs& r = x.b.r;
+    const int rc = actor_rows_args(actor, critic, replay, size, B, idx, seed_lo, seed_hi, counter,
+                                   batch, q, da, acts, save_mask, dz, dz_save_mask, masks_actor,
+                                   masks_critic, edge_slabs, r);
+    if (rc) return rc;
+    r.dq = (float)(-(double)q_weight / (double)B);
+    x.b.bc.B_demo = B_demo;
+    x.b.bc.bc_coef = B_demo > 0 ? (float)(2.0 * (double)bc_weight / (double)B_demo) : 0.f;
+    x.b.bc.bc_part = bc_part;
+    x.qf.q_demo = q_demo;
+    x.qf.keep_part = keep_part;
+    return rows_dispatch(r.actor.hp, FAM_ACTOR_BCQ, 0, 0, &x, 1, r.B, S(stream));
 }
 
 int64_t nav_td3_pop_table_bytes(int32_t n_members) {

@@ -651,6 +651,10 @@ constexpr size_t actor_rows_lds(int tm, int hp) {
 constexpr size_t actor_rows_bc_lds(int tm, int hp) {
     return actor_rows_lds(tm, hp) + (2 * tm + kBlock / 64) * 4;
 }
+// the Q-filtered BC form: past those, the rows' Q1(s, a_demo) [tm], later their keep flags
+constexpr size_t actor_rows_bcq_lds(int tm, int hp) {
+    return actor_rows_bc_lds(tm, hp) + tm * 4;
+}
 
 
 // Store a layer's C-layout result into the LDS rows (the next layer's A operand) and its ReLU
@@ -1978,7 +1982,7 @@ struct ActorRowsArgs {
 // The behaviour-cloning forms of actor_rows (nav_td3_actor_rows_bc): the plain arguments (dq =
 // -q_weight/B) and, beside them, what the BC term on the batch's first B_demo rows needs. Not in
 // ActorRowsArgs: the population table stores that struct per member.
-enum { ACTOR_PLAIN = 0, ACTOR_TD3_BC = 1, ACTOR_BC_ONLY = 2 };
+enum { ACTOR_PLAIN = 0, ACTOR_TD3_BC = 1, ACTOR_BC_ONLY = 2, ACTOR_TD3_BCQ = 3 };
 struct ActorBcExtra {
     int64_t B_demo;      // rows b < B_demo are demonstration rows
     float bc_coef;       // 2 * bc_weight / B_demo
@@ -1988,6 +1992,20 @@ struct ActorRowsBcArgs {
     ActorRowsArgs r;     // r.critic: the actor's descriptor again when bc_only (never read)
     ActorBcExtra bc;
     int bc_only;         // no critic given: the BC term alone
+};
+// The Q-filtered BC form (nav_td3_actor_rows_bcq, MODE = ACTOR_TD3_BCQ): a demonstration row b <
+// B_demo adds its BC term only where keep_b = Q1(s_b, a_b) > Q1(s_b, pi(s_b)) (online critic 1,
+// strict; a NaN on either side compares false: dropped). The decision carries no gradient, and
+// the term's normaliser stays B_demo, not the kept rows' count: bc_coef stays a launch constant
+// and no count crosses the blocks before the backward pass. Not in ActorBcExtra: the
+// population's BC table stores ActorRowsBcArgs per member.
+struct ActorBcqExtra {
+    float* q_demo;       // [B] Q1(s, a_demo), rows < B_demo written; nullable
+    int32_t* keep_part;  // [row blocks] demonstration rows of the block the filter kept
+};
+struct ActorRowsBcqArgs {
+    ActorRowsBcArgs b;   // bc_only 0: the filter needs the critic
+    ActorBcqExtra qf;
 };
 
 // train_actor (robot.py:382-390) for one block of TM batch rows: sample, actor forward,
@@ -2001,6 +2019,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_td3_actor_rows(ActorRowsArgs a) {
     constexpr RowsPop pv{};
     constexpr int MODE = ACTOR_PLAIN;
     constexpr ActorBcExtra bx{};
+    constexpr ActorBcqExtra qx{};
 #include "td3_actor_rows_body.inc"
 }
 template <int NT, int RT, int CBM>
@@ -2008,6 +2027,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_td3_actor_rows_pop(RowsPop pv) {
     constexpr bool POP = true;
     constexpr int MODE = ACTOR_PLAIN;
     constexpr ActorBcExtra bx{};
+    constexpr ActorBcqExtra qx{};
     const ActorRowsArgs& a = static_cast<const ActorRowsArgs*>(pv.table)[blockIdx.z];
 #include "td3_actor_rows_body.inc"
 }
@@ -2019,6 +2039,19 @@ __global__ __launch_bounds__(kBlock, 1) void k_td3_actor_rows_bc(ActorRowsBcArgs
     constexpr RowsPop pv{};
     const ActorRowsArgs& a = x.r;
     const ActorBcExtra& bx = x.bc;
+    constexpr ActorBcqExtra qx{};
+#include "td3_actor_rows_body.inc"
+}
+// the Q-filtered BC form: in the workgroups that hold demonstration rows (row0 < B_demo, the
+// batch's prefix) one more forward of the critic, on (s, a_demo), ahead of the actor's
+template <int NT, int RT, int CBM>
+__global__ __launch_bounds__(kBlock, 1) void k_td3_actor_rows_bcq(ActorRowsBcqArgs x) {
+    constexpr bool POP = false;
+    constexpr RowsPop pv{};
+    constexpr int MODE = ACTOR_TD3_BCQ;
+    const ActorRowsArgs& a = x.b.r;
+    const ActorBcExtra& bx = x.b.bc;
+    const ActorBcqExtra& qx = x.qf;
 #include "td3_actor_rows_body.inc"
 }
 // the population's BC form (nav_td3_actor_rows_bc_pop): grid.z is the member, whose
@@ -2031,6 +2064,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_td3_actor_rows_bc_pop(RowsPop pv)
     const ActorRowsBcArgs& x = static_cast<const ActorRowsBcArgs*>(pv.table)[blockIdx.z];
     const ActorRowsArgs& a = x.r;
     const ActorBcExtra& bx = x.bc;
+    constexpr ActorBcqExtra qx{};
 #include "td3_actor_rows_body.inc"
 }
 
@@ -2061,7 +2095,8 @@ int row_tiles_for(int64_t M, bool tick) { return (!tick && M <= kSmallRows) ? 1 
 // them through nav_mlp_rows_<role>_<NT>(). Argument structs travel as const void* (same definitions).
 enum {
     FAM_FWD = 0, FAM_BWD = 1, FAM_CRITIC = 2, FAM_ACTOR = 3, FAM_TEST = 4, FAM_TEST_POP = 5,
-    FAM_CRITIC_POP = 6, FAM_ACTOR_POP = 7, FAM_ACTOR_BC = 8, FAM_ACTOR_BC_POP = 9, FAM_CRITIC_W = 10
+    FAM_CRITIC_POP = 6, FAM_ACTOR_POP = 7, FAM_ACTOR_BC = 8, FAM_ACTOR_BC_POP = 9, FAM_CRITIC_W = 10,
+    FAM_ACTOR_BCQ = 11
 };
 
 }  // namespace

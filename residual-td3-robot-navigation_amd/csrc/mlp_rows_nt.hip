@@ -1,5 +1,5 @@
 // mlp_rows_nt.hip — the launchers of the row kernels (mlp_rows.h) of one hidden width, hp = 32 *
-// NAV_MLP_PART, and one role (NAV_MLP_ROLE, mlp_rows_role.h): 8 x 6 independent objects, so make
+// NAV_MLP_PART, and one role (NAV_MLP_ROLE, mlp_rows_role.h): 8 x 7 independent objects, so make
 // -j compiles the heavy template instantiations in parallel. Each exports one dispatcher,
 // nav_mlp_rows_<role>_<NT>(), that mlp_abi.hip calls; the role decides which kernels the object
 // instantiates.
@@ -107,6 +107,19 @@ void launch_actor_rows_bc(const ActorRowsBcArgs& a, hipStream_t st) {
     launch_k(k, dim3(gx, 1u + wy), actor_rows_bc_lds(TM, NT * 32), st, w);
 }
 
+// the Q-filtered BC form: the BC form's grid and warmers, its LDS and the rows' Q1(s, a_demo)
+template <int NT, int RT>
+void launch_actor_rows_bcq(const ActorRowsBcqArgs& a, hipStream_t st) {
+    constexpr int TM = RT * 32;
+    auto k = a.b.r.critic.n_hidden == 1 ? k_td3_actor_rows_bcq<NT, RT, 0>
+                                        : k_td3_actor_rows_bcq<NT, RT, 1>;
+    const unsigned gx = row_blocks(a.b.r.B, TM);
+    ActorRowsBcqArgs w = a;
+    const WarmNet nets[] = {{a.b.r.actor, false}, {a.b.r.critic, false}};
+    const unsigned wy = set_warmers(w.b.r.warm, nets, 2, gx, 1u);
+    launch_k(k, dim3(gx, 1u + wy), actor_rows_bcq_lds(TM, NT * 32), st, w);
+}
+
 // the population forms: grid.z = the member, no L2 warmer rows
 template <int NT, int RT>
 void launch_critic_rows_pop(const RowsPopLaunch& a, hipStream_t st) {
@@ -145,7 +158,9 @@ void launch_test(const TestArgs& a, hipStream_t st) {
 template <int NT, int RT, int ROLE>
 int rows_rt(int fam, int in_mode, int out_mode, const void* args, int n_nets, hipStream_t st) {
     if (rows_role(fam, out_mode) != ROLE) return NAV_EINVAL;
-    if constexpr (ROLE == ROLE_PER) {
+    if constexpr (ROLE == ROLE_BCQ) {
+        launch_actor_rows_bcq<NT, RT>(*static_cast<const ActorRowsBcqArgs*>(args), st);
+    } else if constexpr (ROLE == ROLE_PER) {
         launch_critic_rows_w<NT, RT>(*static_cast<const CriticRowsWArgs*>(args), st);
     } else if constexpr (ROLE == ROLE_BC) {
         launch_actor_rows_bc<NT, RT>(*static_cast<const ActorRowsBcArgs*>(args), st);

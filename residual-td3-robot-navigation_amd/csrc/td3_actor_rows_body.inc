@@ -4,6 +4,10 @@
 // ACTOR_TD3_BC adds the BC term's gradient on rows < bx.B_demo to dL/da, ACTOR_BC_ONLY also runs
 // no critic pass. The plain forms' statements are what they were. POP with ACTOR_TD3_BC is
 // k_td3_actor_rows_bc_pop: `a` and `bx` from the member's entry of the BC table.
+// ACTOR_TD3_BCQ (k_td3_actor_rows_bcq, extras in `qx`) is ACTOR_TD3_BC with the Q-filter: a
+// workgroup with demonstration rows (row0 < bx.B_demo: block-uniform, the rows are the batch's
+// prefix) first runs the critic forward on (s, a_demo), and a row's BC term counts only where that
+// value exceeds Q1(s, pi(s)). The term's normaliser stays B_demo (bc_coef a launch constant).
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if constexpr (!POP) {
         if (a.warm.n && (int)blockIdx.y >= a.warm.y0) {  // an L2 warmer row (small grids)
@@ -24,6 +28,9 @@
     // BC forms: the sampled rows' actions [2][TM] and the waves' BC sums, past the stage
     [[maybe_unused]] float* bca =
         reinterpret_cast<float*>(reinterpret_cast<char*>(stage) + stage_bytes(TM, hp));
+    // ACTOR_TD3_BCQ: past those, the rows' Q1(s, a_demo) [TM], then (same slots, written by the
+    // thread that read them) 1.f where the filter keeps the row's BC term, else 0.f
+    [[maybe_unused]] float* qd = bca + 2 * TM + kBlock / 64;
     const L0Pre l0_a = load_l0<NT>(a.actor);  // in flight under the sampling
     NAV_CLOCK(1, 0);
     if (tid < TM) {
@@ -43,11 +50,29 @@
             bca[tid] = lo.z;
             bca[TM + tid] = lo.w;
         }
+        if constexpr (MODE == ACTOR_TD3_BCQ)  // (s, a_demo); the actor's forward reads s alone
+            *reinterpret_cast<float4*>(xin + tid * 4) = lo;
+        else
         *reinterpret_cast<float4*>(xin + tid * 4) = make_float4(lo.x, lo.y, 0.f, 0.f);  // s
         *reinterpret_cast<float4*>(dys + tid * 4) =
             make_float4(b < B ? a.dq : 0.f, 0.f, 0.f, 0.f);
     }
     __syncthreads();
+    if constexpr (MODE == ACTOR_TD3_BCQ) {
+        // Q1(s, a_demo) of the block's rows, as critic_rows runs its target passes: no masks, no
+        // saved rows, no top-layer state kept (a.masks_c is the later (s, pi(s)) pass's). The
+        // actor's forward overwrites the rows and (after its barriers) the partial sums.
+        if (row0 < bx.B_demo) {
+            f32x16 topq[RT][2];
+            fwd_net<NT, RT, 1, 4>(a.critic, act, stage, xin, red, nullptr, n_rt, nullptr, 0u, row0,
+                                  B, rt0, topq);
+            if (tid < TM) {
+                const float v = out_y<RT>(a.critic, red, tid, 0);
+                qd[tid] = v;
+                if (qx.q_demo && row0 + tid < bx.B_demo) qx.q_demo[row0 + tid] = v;
+            }
+        }
+    }
     // the actor's top hidden layer stays in registers until dL/da is known (its dWo partials)
     f32x16 topa[RT][2];
     fwd_net<NT, RT, 1, 2>(a.actor, act, stage, xin, red, a.masks_a, n_rt, a.acts, a.save_mask, row0, B, rt0,
@@ -81,7 +106,17 @@
                 top_bits[rt * 2 + j] = bits;
             }
     }
+    if constexpr (MODE == ACTOR_TD3_BCQ) {
+        // the filter's decision, from the value that goes to a.q: strict, NaN compares false
+        if (tid < TM) {
+            const float qp = out_y<RT>(a.critic, red, tid, 0);
+            if (a.q && row0 + tid < B) a.q[row0 + tid] = qp;
+            const bool keep = row0 + tid < bx.B_demo && qd[tid] > qp;
+            qd[tid] = keep ? 1.f : 0.f;  // (read below after bwd_net's barriers)
+        }
+    } else {
     if (tid < TM && a.q && row0 + tid < B) a.q[row0 + tid] = out_y<RT>(a.critic, red, tid, 0);
+    }
     bwd_net<NT, RT, 1, CBM>(a.critic, act, stage, dys, xin, a.masks_c, n_rt, nullptr, nullptr,
                                     nullptr, 0u, row0, B, rt0, -64, top_bits, &wo);
     }
@@ -102,9 +137,11 @@
             const int rloc = tid % TM, j = tid / TM;
             const int64_t r = row0 + rloc;
             float v = 0.f;
-            if constexpr (MODE == ACTOR_TD3_BC)
+            if constexpr (MODE == ACTOR_TD3_BC || MODE == ACTOR_TD3_BCQ)
                 v = r < B ? dx_unit<NT>(a.critic, act, rloc, 2 + j) : 0.f;
-            if (r < bx.B_demo) {
+            bool term = r < bx.B_demo;
+            if constexpr (MODE == ACTOR_TD3_BCQ) term = qd[rloc] != 0.f;  // 0 on rows >= B_demo
+            if (term) {
                 const float d = xin[rloc * 4 + 2 + j] - bca[j * TM + rloc];
                 v += bx.bc_coef * d;
                 e2 = d * d;
@@ -114,6 +151,12 @@
         }
         const float w = wave_sum(e2);
         if ((tid & 63) == 0) bca[2 * TM + (tid >> 6)] = w;
+        if constexpr (MODE == ACTOR_TD3_BCQ) {
+            // the block's kept rows, counted once each (j == 0's threads: all in wave 0)
+            static_assert(TM <= 64, "the rows' threads are one wave");
+            const float kept = wave_sum(tid < TM ? qd[tid] : 0.f);
+            if (tid == 0) qx.keep_part[blockIdx.x] = (int32_t)kept;
+        }
     }
     if (tid < TM) {
         dys2[tid * 4 + 2] = 0.f;

@@ -184,6 +184,11 @@ SIGNATURES = [
                                         C.c_int64, _vp, C.c_uint32, C.c_uint32, C.c_uint32,
                                         C.c_int64, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp,
                                         C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
+    ("nav_td3_actor_rows_bcq", C.c_int, [_P(NavMlp), _P(NavMlp), _P(NavReplay), C.c_int64,
+                                         C.c_int64, _vp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.c_int64, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp,
+                                         _vp]),
     ("nav_td3_mix_idx", C.c_int, [C.c_int64] * 5 + [C.c_uint32] * 3 + [_vp, _vp, _vp]),
     ("nav_demo_transitions", C.c_int, [_P(NavParams), C.c_int32, C.c_int32, _vp, _vp, _vp,
                                        C.c_int32, _vp, _vp]),

@@ -84,6 +84,10 @@ class TD3Config:
     bc_weight: float = 0.0
     q_weight: float = 1.0
     demo_fraction: float = 0.0
+    # the Q-filter of the BC term (Nair et al. 2018; off by default): a demonstration row adds its
+    # BC term only where online critic 1 rates its action above the policy's, Q1(s, a) >
+    # Q1(s, pi(s)), strictly; the term's normaliser stays the batch's demonstration rows
+    bc_q_filter: bool = False
     # prioritised replay (off by default, per_alpha == 0): batches are drawn in proportion to
     # priority (|TD error| + per_eps)^per_alpha and the critics' loss carries the importance
     # weights (N p_k / S)^-per_beta over their maximum; per_beta is read every epoch
@@ -95,6 +99,21 @@ class TD3Config:
     # where the env was reset or the ring's write head is reached (1 .. NAV_NSTEP_MAX = 16)
     n_step: int = 1
     net: NetConfig = field(default_factory=NetConfig)
+
+    def b_demo(self):
+        """Demonstration rows per batch, round(demo_fraction * batch_size); ValueError for a
+        demo_fraction outside [0, 1], a bc_weight without such rows, or bc_q_filter without the
+        BC term it filters (needs no device)."""
+        n = int(round(self.demo_fraction * self.batch_size))
+        if not 0 <= n <= self.batch_size:
+            raise ValueError("demo_fraction must lie in [0, 1]")
+        if self.bc_weight != 0 and n == 0:
+            raise ValueError("bc_weight needs demonstration rows in the batch: demo_fraction * "
+                             "batch_size rounds to 0")
+        if self.bc_q_filter and (n == 0 or self.bc_weight == 0):
+            raise ValueError("bc_q_filter filters the BC term: it needs bc_weight != 0 and "
+                             "demonstration rows in the batch (demo_fraction * batch_size >= 1)")
+        return n
 
     def check_n_step(self, grad_hook=None):
         """ValueError for an n_step outside 1 .. NAV_NSTEP_MAX, or n_step > 1 with what

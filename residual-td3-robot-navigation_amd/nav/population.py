@@ -26,7 +26,8 @@ hands it the source's hyper-parameters and perturbs those named by `explore`; pb
 three in a row. Nothing of it runs unless called.
 
 Learning from the demonstrations per member: a member's overrides may carry demo_fraction,
-bc_weight and q_weight (TD3Config). Then every member's ring has a tail with the frame-0
+bc_weight and q_weight (TD3Config; also bc_q_filter, the BC term's Q-filter, with
+learner="members" only). Then every member's ring has a tail with the frame-0
 transitions of its own env groups' demonstrations; learner="members" runs each TD3's one
 epoch loop on its tailed ring, learner="batched" issues one nav_td3_mix_idx_pop per epoch and
 nav_td3_actor_rows_bc_pop in place of nav_td3_actor_rows_pop, from a second device table of the
@@ -337,6 +338,10 @@ class PopulationLearner:
         """The members' nav_td3_member_bc entries (index pointers still unset), or None if no
         member learns from demonstrations. A member with it off takes B_demo = 0, bc_weight = 0
         and q_weight = 1: the plain actor loss, bit for bit."""
+        for m, t in enumerate(self.td3):
+            if t.cfg.bc_q_filter:
+                raise ValueError("PopulationLearner: bc_q_filter has no population form of the "
+                                 f"actor kernel (member {m}): take the per-member path")
         if not any(t.bc_on() for t in self.td3):
             return None
         out = []
@@ -434,6 +439,18 @@ class PopulationTrainer:
             if ck.get("n_step", 1) != 1:
                 raise ValueError("multi-step returns (n_step > 1) are not available to "
                                  f"population members: member {m}")
+            # the BC term's Q-filter: each member's own launches run it (learner="members"); the
+            # one-launch learner has no population form of that kernel
+            if ck.get("bc_q_filter", False):
+                if learner == "batched":
+                    raise ValueError('bc_q_filter is not available with learner="batched" (no '
+                                     'population form of the Q-filtered actor kernel): member '
+                                     f'{m}')
+                try:  # without the BC term it filters: refused as TD3Config.b_demo refuses it
+                    K.TD3Config(batch_size=int(batch), bc_q_filter=True,
+                                **{k: ck[k] for k in BC_KEYS if k in ck}).b_demo()
+                except ValueError as e:
+                    raise ValueError(f"member {m}: {e}") from None
         # learning from the demonstrations: on for a member whose demo_fraction or bc_weight is
         # non-zero (TD3.bc_on); then every member's ring carries a tail of its own envs'
         # demonstrations

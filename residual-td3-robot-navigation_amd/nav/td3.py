@@ -17,10 +17,11 @@ from . import prof
 from ._lib import NavReplay, descs, lib, parr, ptr, stream_handle
 from .mlp import DeviceMLP
 
-# the constant arguments of nav_td3_actor_rows and nav_td3_actor_rows_bc, by the ABI's names
+# the constant arguments of nav_td3_actor_rows, nav_td3_actor_rows_bc and nav_td3_actor_rows_bcq,
+# by the ABI's names (q_demo / keep_part: the Q-filtered form's alone)
 _ActorRows = collections.namedtuple(
     "_ActorRows", "actor critic batch q da bc_part acts save_mask dz dz_save_mask masks_actor "
-                  "masks_critic edge_slabs")
+                  "masks_critic edge_slabs q_demo keep_part", defaults=(None, None))
 
 
 class _Adam:
@@ -152,6 +153,9 @@ class TD3:
         self.idx_c = torch.zeros(B, dtype=torch.int64, device=d)
         self.idx_a = torch.zeros(B, dtype=torch.int64, device=d)
         self.bc_part = f(self.nblk)
+        # the Q-filter: Q1(s, a) of the demonstration rows and the blocks' counts of kept rows
+        self.q_demo = f(B)
+        self.keep_part = torch.zeros(self.nblk, dtype=torch.int32, device=d)
         # prioritised replay: the batch's importance weights and the twins' |TD errors|
         if self.per_on():
             self.w_per, self.w_one = f(B), torch.ones(B, dtype=torch.float32, device=d)
@@ -225,7 +229,8 @@ class TD3:
         if B != self._B:
             self._workspace(B)
         key = (B, self.seed, c.policy_noise, c.noise_clip, c.max_action, c.gamma, c.tau,
-               self.split_twins, c.bc_weight, c.q_weight, c.demo_fraction, c.per_alpha, c.n_step)
+               self.split_twins, c.bc_weight, c.q_weight, c.demo_fraction, c.per_alpha, c.n_step,
+               c.bc_q_filter)
         if self._st is not None and self._st_key == key:
             return self._st
         c1, c2, a = self.critic_network_1, self.critic_network_2, self.actor_network
@@ -240,7 +245,8 @@ class TD3:
                         q=ptr(self.q1), da=ptr(self.da), bc_part=ptr(self.bc_part),
                         acts=ptr(self.acts_a), save_mask=mida, dz=ptr(self.dz_a),
                         dz_save_mask=mida, masks_actor=ptr(self.mask_a),
-                        masks_critic=ptr(self.mask1), edge_slabs=ptr(self.eslab_a))
+                        masks_critic=ptr(self.mask1), edge_slabs=ptr(self.eslab_a),
+                        q_demo=ptr(self.q_demo), keep_part=ptr(self.keep_part))
         st = {
             "keep": (ta, ca, c1d),
             "seed": (self.seed & 0xFFFFFFFF, (self.seed >> 32) & 0xFFFFFFFF),
@@ -255,7 +261,8 @@ class TD3:
             "ar_work": (fwd(2, 2, h, nh, B) + fwd(4, 1, h, nh, B) + bwd(4, 1, h, nh, B, True) +
                         bwd(2, 2, h, nh, B, False, True, True)),
             "ar": ar,  # and the critic-free BC form's (pretrain_bc)
-            "ar_bc_alone": ar._replace(critic=None, q=None, masks_critic=None),
+            "ar_bc_alone": ar._replace(critic=None, q=None, masks_critic=None, q_demo=None,
+                                       keep_part=None),
             "td_abs": parr(self.td_abs1, self.td_abs2) if self.per_on() else None,
             "c": self._group([c1, c2], (self.critic_optimizer_1, self.critic_optimizer_2),
                              self.batch, [self.acts1, self.acts2], [self.dz1, self.dz2],
@@ -395,10 +402,16 @@ class TD3:
 
     # robot.py:369-398
     @staticmethod
-    def _actor_rows_call(a, sample, bc):
+    def _actor_rows_call(a, sample, bc, q_filter=False):
         """(region, entry point, its arguments before the stream) from `a` (_ActorRows), `sample`
         = (replay, size, B, idx, seed_lo, seed_hi, counter) and `bc` = None (the plain form) or
-        (B_demo, q_weight, bc_weight): each entry point's argument order, written once."""
+        (B_demo, q_weight, bc_weight), with q_filter the Q-filtered BC form: each entry point's
+        argument order, written once."""
+        if q_filter:
+            return "actor_rows_bcq", lib().nav_td3_actor_rows_bcq, (
+                a.actor, a.critic, *sample, *bc, a.batch, a.q, a.da, a.bc_part, a.q_demo,
+                a.keep_part, a.acts, a.save_mask, a.dz, a.dz_save_mask, a.masks_actor,
+                a.masks_critic, a.edge_slabs)
         if bc is None:
             return "actor_rows", lib().nav_td3_actor_rows, (
                 a.actor, a.critic, *sample, a.batch, a.q, a.da, a.acts, a.save_mask, a.dz,
@@ -410,7 +423,8 @@ class TD3:
     def _actor_rows(self, replay, idx, s, bc=None, critic=True, ref=None, size=None):
         # sample + actor forward + critic-1 forward + backward of -mean(Q) to the action + the
         # actor's row backward with its edge partials: one launch. With bc = (B_demo, q_weight,
-        # bc_weight) the BC form into the same workspace (critic False: the BC term alone);
+        # bc_weight) the BC form into the same workspace (critic False: the BC term alone; with
+        # cfg.bc_q_filter and a critic its Q-filtered form);
         # ref / size: a replay descriptor and its fill in place of `replay`
         st = self._static()
         if bc is not None:
@@ -419,7 +433,8 @@ class TD3:
             ref, size = self._replay_ref(replay), len(replay)
         name, fn, args = self._actor_rows_call(
             st["ar"] if critic else st["ar_bc_alone"],
-            (ref, size, self._B, ptr(idx), *st["seed"], self.update_counter), bc)
+            (ref, size, self._B, ptr(idx), *st["seed"], self.update_counter), bc,
+            bc is not None and critic and self.cfg.bc_q_filter)
         self._run(name, st["ar_work"], fn, *args, s)
         return st["a"]
 
@@ -453,9 +468,19 @@ class TD3:
 
     def bc_loss_value(self):
         """The last BC launch's term: sum_j (pi_j(s) - a_j)^2 averaged over its demonstration
-        rows (0 without any), synchronising."""
+        rows (0 without any), synchronising. With cfg.bc_q_filter the sum runs over the rows the
+        filter kept; the divisor stays the demonstration rows."""
         n = self._last_b_demo
         return (self.bc_part.double().sum() / n).item() if n else 0.0
+
+    def bc_kept_fraction(self):
+        """The share of the last Q-filtered launch's demonstration rows whose BC term the filter
+        kept, Q1(s, a) > Q1(s, pi(s)) (0.0 without demonstration rows or before any such
+        launch), synchronising."""
+        n = self._last_b_demo
+        if not n or not self.cfg.bc_q_filter or not self._B:
+            return 0.0
+        return self.keep_part.sum().item() / n
 
     # ---- prioritised replay
     def per_on(self):
@@ -467,17 +492,12 @@ class TD3:
 
     # ---- learning from demonstrations
     def bc_on(self):
-        return self.cfg.demo_fraction != 0 or self.cfg.bc_weight != 0
+        # (bc_q_filter alone counts as on, so that b_demo() refuses it)
+        return self.cfg.demo_fraction != 0 or self.cfg.bc_weight != 0 or self.cfg.bc_q_filter
 
     def b_demo(self):
         """Demonstration rows per batch: the batch's first round(demo_fraction * B) rows."""
-        n = int(round(self.cfg.demo_fraction * self.cfg.batch_size))
-        if not 0 <= n <= self.cfg.batch_size:
-            raise ValueError("demo_fraction must lie in [0, 1]")
-        if self.cfg.bc_weight != 0 and n == 0:
-            raise ValueError("bc_weight needs demonstration rows in the batch: demo_fraction * "
-                             "batch_size rounds to 0")
-        return n
+        return self.cfg.b_demo()
 
     def _mix(self, size, b_demo, demo_base, n_demo, counter, idx_c, idx_a, s):
         self.mix_launches += 1
@@ -490,7 +510,8 @@ class TD3:
         demonstration row), the critic-free BC form of the actor row kernel, then the actor's
         usual weight gradients, reduce and Adam step; at the end the target actor is the actor.
         batch: rows per epoch (default cfg.batch_size); lr: the actor's Adam step size for these
-        epochs only."""
+        epochs only. There is no critic here, so cfg.bc_q_filter does not apply: every row is
+        cloned."""
         n = int(rows.shape[0])
         assert rows.shape == (n, 8) and rows.is_contiguous() and n >= 1
         c, opt = self.cfg, self.actor_optimizer
@@ -515,7 +536,8 @@ class TD3:
 
     def bc_loss(self, rows, stream=None):
         """The BC term sum_j (pi_j(s) - a_j)^2 of the online actor averaged over all of `rows`
-        [n][8], taken in order (idx = arange): deterministic. Changes no learner state."""
+        [n][8], taken in order (idx = arange): deterministic. Changes no learner state. Unfiltered
+        (no critic pass), whatever cfg.bc_q_filter says."""
         n = int(rows.shape[0])
         assert rows.shape == (n, 8) and rows.is_contiguous() and n >= 1
         a, L, d = self.actor_network, lib(), self.device

@@ -62,11 +62,15 @@ class VecTrainer:
                  replay_capacity=None, seed=K.RANDOM_SEED, envs_per_group=1024, demos=True,
                  device="cuda", field=None, grad_hook=None, fuse_tick=True, overlap_collect=False,
                  demo_fraction=0.0, bc_weight=0.0, q_weight=1.0, demo_rows=None,
-                 per_alpha=0.0, per_beta=0.4, per_eps=1e-6, n_step=1):
+                 per_alpha=0.0, per_beta=0.4, per_eps=1e-6, n_step=1, bc_q_filter=False):
         """demo_fraction / bc_weight / q_weight: learning from the demonstrations (TD3Config; off
         by default). With demo_fraction or bc_weight non-zero the CEM demonstrations' transitions
         sit in a tail behind the replay ring and a share of every batch is drawn from it (needs
         demos=True, or demo_rows = (frame-0 rows, frame-1 rows) from a checkpoint).
+        bc_q_filter: the Q-filter of the BC term (TD3Config; off by default): a demonstration row
+        is cloned only where critic 1 rates its action above the policy's. Needs bc_weight != 0
+        and demonstration rows in the batch (ValueError); td3.bc_kept_fraction() reports the
+        share of rows the last policy epoch kept.
         per_alpha / per_beta / per_eps: prioritised replay (TD3Config; off at per_alpha == 0).
         On, the ring carries one priority per row, every tick stamps its rows with the running
         maximum, and batches are drawn in proportion to priority. Not with demo_fraction /
@@ -79,6 +83,9 @@ class VecTrainer:
         # (the gather reads rows an overlapped tick may be writing); the learner refuses the rest
         K.TD3Config(n_step=n_step, demo_fraction=float(demo_fraction),
                     bc_weight=float(bc_weight)).check_n_step(grad_hook)
+        if bc_q_filter:  # the Q-filter without the BC term it filters: refused here too
+            K.TD3Config(batch_size=int(batch), demo_fraction=float(demo_fraction),
+                        bc_weight=float(bc_weight), bc_q_filter=True).b_demo()
         if n_step > 1 and overlap_collect:
             raise ValueError("multi-step returns (n_step > 1) do not combine with "
                              "overlap_collect")
@@ -94,7 +101,8 @@ class VecTrainer:
                           net=K.NetConfig(hidden=hidden, n_hidden=n_hidden),
                           bc_weight=float(bc_weight), q_weight=float(q_weight),
                           demo_fraction=float(demo_fraction), per_alpha=float(per_alpha),
-                          per_beta=float(per_beta), per_eps=float(per_eps), n_step=n_step)
+                          per_beta=float(per_beta), per_eps=float(per_eps), n_step=n_step,
+                          bc_q_filter=bool(bc_q_filter))
         if cfg.per_alpha != 0 and overlap_collect:
             raise ValueError("prioritised replay (per_alpha > 0) does not combine with "
                              "overlap_collect")
@@ -260,6 +268,8 @@ class VecTrainer:
         if self.td3.nstep_on():  # multi-step returns: the horizon and the cut marks
             sd["meta"].update(n_step=self.td3.cfg.n_step)
             sd["replay"].update(cut=self.replay.cut.cpu())
+        if self.td3.cfg.bc_q_filter:  # the BC term's Q-filter (absent: off)
+            sd["meta"].update(bc_q_filter=True)
         return sd
 
     def load_state_dict(self, sd):
@@ -300,7 +310,8 @@ class VecTrainer:
                 q_weight=m.get("q_weight", 1.0),
                 demo_rows=None if dr is None else (dr["rows0"], dr["rows1"]),
                 per_alpha=m.get("per_alpha", 0.0), per_beta=m.get("per_beta", 0.4),
-                per_eps=m.get("per_eps", 1e-6), n_step=int(m.get("n_step", 1)))
+                per_eps=m.get("per_eps", 1e-6), n_step=int(m.get("n_step", 1)),
+                bc_q_filter=bool(m.get("bc_q_filter", False)))
         t.load_state_dict(sd)
         return t
 

@@ -6,6 +6,9 @@ python tools/actor_rows_bc_bench.py [--batch 32768 --hidden 256 --layers 2 --b-d
 In one process, with HIP events on the launch stream:
 - nav_td3_actor_rows (plain) against nav_td3_actor_rows_bc (the TD3_BC form) on the same
   injected indices, `runs` alternating runs of `reps` launches each;
+- in the same alternation nav_td3_actor_rows_bcq (the Q-filtered BC form, the critic's forward on
+  (s, a_demo) inside the launch) and what it replaces, three launches: a gather of the B_demo
+  demonstration rows, nav_mlp_forward of critic 1 on them, then the BC form;
 - nav_td3_mix_idx at the same batch;
 - ms per VecTrainer.step() with demo_fraction 0.25 / bc_weight 1 against the default trainer,
   alternating (n_envs = 2 * batch as bench.py's flagship shape), when --trainer-steps > 0.
@@ -88,13 +91,32 @@ def main():
     def bc():
         L.nav_td3_actor_rows_bc(*head, bd, 1.0, 1.0, ptr(batch), ptr(q), ptr(da), ptr(part),
                                 *tail)
-    t_plain, t_bc, t_mix = [], [], []
+    q_demo, keep = f(B), torch.zeros(nblk, dtype=torch.int32, device=dev)
+
+    def bcq():
+        L.nav_td3_actor_rows_bcq(*head, bd, 1.0, 1.0, ptr(batch), ptr(q), ptr(da), ptr(part),
+                                 ptr(q_demo), ptr(keep), *tail)
+    # the unfused alternative: gather, critic forward on the gathered rows, the BC form
+    gathered, q_alt, demo_idx = f(bd, 8), f(bd), idx_a[:bd]
+    out1 = (C.c_void_p * 1)(q_alt.data_ptr())
+
+    def two_launch():
+        torch.index_select(rows, 0, demo_idx, out=gathered)
+        L.nav_mlp_forward(C.byref(cd), 1, bd, ptr(gathered), 8, 0, out1, 1, 0, 0, None, 0.0, 0.0,
+                          0.0, 0, 0, 0, None, 0, None, s)
+        bc()
+    t_plain, t_bc, t_bcq, t_two, t_mix = [], [], [], [], []
     for _ in range(args.runs):
         t_plain.append(timeit(plain, args.reps))
         t_bc.append(timeit(bc, args.reps))
+        t_bcq.append(timeit(bcq, args.reps))
+        t_two.append(timeit(two_launch, args.reps))
         t_mix.append(timeit(mix, args.reps))
+    torch.cuda.synchronize()
     res = {"batch": B, "hidden": H, "layers": nh, "b_demo": bd, "reps": args.reps,
            "actor_rows_us": summary(t_plain), "actor_rows_bc_us": summary(t_bc),
+           "actor_rows_bcq_us": summary(t_bcq), "gather_forward_bc_us": summary(t_two),
+           "bcq_kept_fraction": round(keep.sum().item() / bd, 4),
            "mix_idx_us": summary(t_mix)}
     if args.trainer_steps > 0:
         from nav.trainer import VecTrainer

@@ -7,7 +7,9 @@ python tools/evaluate.py --n-envs 4096 --train-steps 0 --bc-pretrain 500 --bc-lr
 
 --bc-pretrain N first clones the demonstrations into the actor (VecTrainer.pretrain_bc: the
 reference README's baseline policy by imitation) and adds the BC loss over all demonstration rows
-before and after to the line; --bc-weight / --demo-fraction train with the demonstrations mixed in;
+before and after to the line; --bc-weight / --demo-fraction train with the demonstrations mixed in
+(--bc-q-filter: a demonstration row is cloned only where critic 1 rates its action above the
+policy's; the line gains bc_kept_fraction, the share the last policy epoch kept);
 --per-alpha / --per-beta / --per-eps train with prioritised replay (not together with those two);
 --n-step N trains on N-step returns (with prioritised replay or alone, not with those two).
 """
@@ -38,6 +40,8 @@ def main():
     ap.add_argument("--bc-lr", type=float, default=None, help="the actor's lr while pretraining")
     ap.add_argument("--bc-weight", type=float, default=0.0)
     ap.add_argument("--demo-fraction", type=float, default=0.0)
+    ap.add_argument("--bc-q-filter", action="store_true",
+                    help="Q-filter on the BC term (needs --bc-weight and --demo-fraction)")
     ap.add_argument("--per-alpha", type=float, default=0.0,
                     help="prioritised replay: priority exponent (0 = off)")
     ap.add_argument("--per-beta", type=float, default=0.4,
@@ -59,7 +63,7 @@ def main():
                         envs_per_group=min(1024, args.n_envs), demos=not args.no_demos,
                         bc_weight=args.bc_weight, demo_fraction=args.demo_fraction,
                         per_alpha=args.per_alpha, per_beta=args.per_beta, per_eps=args.per_eps,
-                        n_step=args.n_step)
+                        n_step=args.n_step, bc_q_filter=args.bc_q_filter)
     bc = {}
     if args.bc_pretrain > 0:
         bc["bc_loss_before"] = tr.bc_loss(frame=1)
@@ -73,6 +77,8 @@ def main():
     res["train_steps"] = tr.steps
     if tr.td3.nstep_on():
         res["n_step"] = tr.td3.cfg.n_step
+    if tr.td3.cfg.bc_q_filter:
+        res["bc_kept_fraction"] = tr.td3.bc_kept_fraction()
     res.update(bc)
     # strict JSON: a NaN (no env reached) prints as null
     print(json.dumps({k: None if isinstance(v, float) and v != v else v for k, v in res.items()}))
