@@ -11,6 +11,14 @@ NAV_ROWS_ROLES(NAV_ROWS_DECL_ROLE)
 
 namespace {
 
+// a hidden width the row kernels are built for: 32 .. 256 in steps of 32
+bool width_ok(int hp) { return hp >= 32 && hp <= 256 && !(hp & 31); }
+
+// a replay fill the samplers can draw from: 1 .. capacity rows, within the 32-bit draw
+bool fill_ok(int64_t size, int64_t capacity) {
+    return size >= 1 && size <= capacity && size <= ((int64_t)1 << 32);
+}
+
 // (role, hp / 32) -> the launcher object
 int rows_dispatch(int hp, int fam, int in_mode, int out_mode, const void* args, int n_nets,
                   int64_t M, hipStream_t st) {
@@ -19,7 +27,7 @@ int rows_dispatch(int hp, int fam, int in_mode, int out_mode, const void* args, 
     static rows_fn* const rows[ROLE_COUNT][8] = {NAV_ROWS_ROLES(NAV_ROWS_ENTRY_ROLE)};
     const int rt = row_tiles_for(
         M, fam == FAM_FWD && (out_mode == OUT_TICK || out_mode == OUT_TICK_POP));
-    if (hp < 32 || hp > 256 || (hp & 31)) return NAV_EINVAL;
+    if (!width_ok(hp)) return NAV_EINVAL;
     const int r =
         rows[rows_role(fam, out_mode)][hp / 32 - 1](fam, rt, in_mode, out_mode, args, n_nets, st);
     if (r) return r;
@@ -131,9 +139,8 @@ int critic_rows_args(const nav_mlp* target_actor, const nav_mlp* target_critics,
                      int32_t split_twins, CriticRowsArgs& a) {
     if (row_backward && dz_save_mask && !dz) return NAV_EINVAL;
     if (!target_actor || !target_critics || !critics || !replay || !replay->rows || B < 1 ||
-        size < 1 || size > replay->capacity || size > ((int64_t)1 << 32) || !batch || !dq ||
-        !loss_part || !masks || !make_dev(target_actor, &a.actor_t) || target_actor->d_in != 2 ||
-        target_actor->d_out != 2)
+        !fill_ok(size, replay->capacity) || !batch || !dq || !loss_part || !masks ||
+        !make_dev(target_actor, &a.actor_t) || target_actor->d_in != 2 || target_actor->d_out != 2)
         return NAV_EINVAL;
     for (int i = 0; i < 2; ++i) {
         if (!make_dev(&target_critics[i], &a.critic_t[i]) || !make_dev(&critics[i], &a.critic[i]) ||
@@ -188,9 +195,8 @@ int actor_rows_args(const nav_mlp* actor, const nav_mlp* critic, const nav_repla
                     uint16_t* masks_actor, uint16_t* masks_critic, float* edge_slabs,
                     ActorRowsArgs& a) {
     // (critic NULL: nav_td3_actor_rows_bc's pure-BC call, no critic to check)
-    if (!actor || !replay || !replay->rows || B < 1 || size < 1 ||
-        size > replay->capacity || size > ((int64_t)1 << 32) || !batch || !da ||
-        (save_mask && !acts) || !masks_actor || !masks_critic || !edge_slabs ||
+    if (!actor || !replay || !replay->rows || B < 1 || !fill_ok(size, replay->capacity) ||
+        !batch || !da || (save_mask && !acts) || !masks_actor || !masks_critic || !edge_slabs ||
         !make_dev(actor, &a.actor) || actor->d_in != 2 || actor->d_out != 2 ||
         (save_mask >> actor->n_hidden) || (dz_save_mask && !dz) ||
         (dz_save_mask >> actor->n_hidden))
@@ -217,6 +223,20 @@ int actor_rows_args(const nav_mlp* actor, const nav_mlp* critic, const nav_repla
     a.masks_c = masks_critic;
     a.eslab = edge_slabs;
     a.ecount = edge_count(a.actor);
+    return 0;
+}
+
+// The BC term beside the plain arguments `r` (filled, so r.B holds), as nav_td3_actor_rows_bc,
+// nav_td3_actor_rows_bcq and the population's BC table form it: what they refuse, then `bc` and,
+// with a critic pass, dq = -q_weight / B
+int bc_extra_args(int64_t B_demo, float q_weight, float bc_weight, float* bc_part, bool critic,
+                  ActorRowsArgs& r, ActorBcExtra& bc) {
+    if (B_demo < 0 || B_demo > r.B || (bc_weight != 0.f && B_demo == 0) || !bc_part)
+        return NAV_EINVAL;
+    if (critic) r.dq = (float)(-(double)q_weight / (double)r.B);
+    bc.B_demo = B_demo;
+    bc.bc_coef = B_demo > 0 ? (float)(2.0 * (double)bc_weight / (double)B_demo) : 0.f;
+    bc.bc_part = bc_part;
     return 0;
 }
 
@@ -271,28 +291,20 @@ int td3_pop_bc_check(const nav_td3_member* members, const nav_td3_member_bc* bc,
     for (int m = 0; m < n_members; ++m) {
         const nav_td3_member& t = members[m];
         const nav_td3_member_bc& x = bc[m];
-        if (x.B_demo < 0 || x.B_demo > B || (x.bc_weight != 0.f && x.B_demo == 0) ||
-            (x.B_demo > 0 && (x.n_demo < 1 || x.n_demo > ((int64_t)1 << 32))) || !x.bc_part ||
+        if ((x.B_demo > 0 && (x.n_demo < 1 || x.n_demo > ((int64_t)1 << 32))) ||
             !x.idx_critic || !x.idx_actor || x.idx_critic != t.idx_critic ||
             x.idx_actor != t.idx_actor)
             return NAV_EINVAL;
         CriticRowsArgs c{};
         ActorRowsBcArgs e{};
-        const int rc = rows_member_fill(t, B, c, e.r);
+        int rc = rows_member_fill(t, B, c, e.r);
+        if (!rc) rc = bc_extra_args(x.B_demo, x.q_weight, x.bc_weight, x.bc_part, true, e.r, e.bc);
         if (rc) return rc;
-        e.r.dq = (float)(-(double)x.q_weight / (double)B);
-        e.bc.B_demo = x.B_demo;
-        e.bc.bc_coef = x.B_demo > 0 ? (float)(2.0 * (double)x.bc_weight / (double)x.B_demo) : 0.f;
-        e.bc.bc_part = x.bc_part;
         if (rows) rows[m] = e;
         if (mix) mix[m] = MixMember{x.B_demo, x.n_demo, t.seed_lo, t.seed_hi,
                                     {x.idx_critic, x.idx_actor}};
     }
     return 0;
-}
-
-bool pop_size_ok(const nav_td3_member* members, int64_t size) {
-    return size >= 1 && size <= members[0].replay.capacity && size <= ((int64_t)1 << 32);
 }
 
 }  // namespace
@@ -314,7 +326,7 @@ int64_t nav_mlp_param_count(int32_t d_in, int32_t d_out, int32_t hp, int32_t n_h
 }
 
 int64_t nav_mlp_packed_count(int32_t hp, int32_t n_hidden) {
-    if (hp < 32 || hp > 256 || (hp & 31) || n_hidden < 1) return NAV_EINVAL;
+    if (!width_ok(hp) || n_hidden < 1) return NAV_EINVAL;
     return (int64_t)(n_hidden - 1) * 2 * split_image_floats(hp);
 }
 
@@ -524,8 +536,7 @@ int64_t nav_mlp_edge_count(int32_t d_in, int32_t d_out, int32_t hidden_pad, int3
 }
 
 int64_t nav_mlp_hidden_count(int32_t hidden_pad, int32_t n_hidden) {
-    if (hidden_pad < 32 || hidden_pad > 256 || (hidden_pad & 31) || n_hidden < 1)
-        return NAV_EINVAL;
+    if (!width_ok(hidden_pad) || n_hidden < 1) return NAV_EINVAL;
     return (int64_t)(n_hidden - 1) * hidden_pad * hidden_pad;
 }
 
@@ -633,27 +644,17 @@ int nav_td3_actor_rows_bc(const nav_mlp* actor, const nav_mlp* critic, const nav
                           uint16_t* masks_actor, uint16_t* masks_critic, float* edge_slabs,
                           void* stream) {
     ActorRowsBcArgs x{};
-    if (B_demo < 0 || B_demo > B || (bc_weight != 0.f && B_demo == 0) || !bc_part)
-        return NAV_EINVAL;
-    // pure BC: the plain check with the actor's mask buffer standing in for the critic's
+    // pure BC: the plain check with no q and the actor's mask buffer standing in for the critic's
     x.bc_only = critic ? 0 : 1;
-    const int rc = critic
-        ? actor_rows_args(actor, critic, replay, size, B, idx, seed_lo, seed_hi, counter, batch,
-                          q, da, acts, save_mask, dz, dz_save_mask, masks_actor, masks_critic,
-                          edge_slabs, x.r)
-        : actor_rows_args(actor, nullptr, replay, size, B, idx, seed_lo, seed_hi, counter, batch,
-                          nullptr, da, acts, save_mask, dz, dz_save_mask, masks_actor,
-                          masks_actor, edge_slabs, x.r);
+    int rc = actor_rows_args(actor, critic, replay, size, B, idx, seed_lo, seed_hi, counter, batch,
+                             critic ? q : nullptr, da, acts, save_mask, dz, dz_save_mask,
+                             masks_actor, critic ? masks_critic : masks_actor, edge_slabs, x.r);
+    if (!rc) rc = bc_extra_args(B_demo, q_weight, bc_weight, bc_part, !x.bc_only, x.r, x.bc);
     if (rc) return rc;
     if (x.bc_only) {
         x.r.critic = x.r.actor;
         x.r.masks_c = nullptr;
-    } else {
-        x.r.dq = (float)(-(double)q_weight / (double)B);
     }
-    x.bc.B_demo = B_demo;
-    x.bc.bc_coef = B_demo > 0 ? (float)(2.0 * (double)bc_weight / (double)B_demo) : 0.f;
-    x.bc.bc_part = bc_part;
     return rows_dispatch(x.r.actor.hp, FAM_ACTOR_BC, 0, 0, &x, 1, x.r.B, S(stream));
 }
 
@@ -665,19 +666,14 @@ int nav_td3_actor_rows_bcq(const nav_mlp* actor, const nav_mlp* critic, const na
                            float* dz, uint32_t dz_save_mask, uint16_t* masks_actor,
                            uint16_t* masks_critic, float* edge_slabs, void* stream) {
     ActorRowsBcqArgs x{};
-    // the BC form's refusals, and the filter's own: it compares critic 1's values
-    if (B_demo < 0 || B_demo > B || (bc_weight != 0.f && B_demo == 0) || !bc_part || !critic ||
-        !keep_part || !q)
-        return NAV_EINVAL;
+    // the filter's own refusals: it compares critic 1's values
+    if (!critic || !keep_part || !q) return NAV_EINVAL;
     ActorRowsArgs& r = x.b.r;
-    const int rc = actor_rows_args(actor, critic, replay, size, B, idx, seed_lo, seed_hi, counter,
-                                   batch, q, da, acts, save_mask, dz, dz_save_mask, masks_actor,
-                                   masks_critic, edge_slabs, r);
+    int rc = actor_rows_args(actor, critic, replay, size, B, idx, seed_lo, seed_hi, counter, batch,
+                             q, da, acts, save_mask, dz, dz_save_mask, masks_actor, masks_critic,
+                             edge_slabs, r);
+    if (!rc) rc = bc_extra_args(B_demo, q_weight, bc_weight, bc_part, true, r, x.b.bc);
     if (rc) return rc;
-    r.dq = (float)(-(double)q_weight / (double)B);
-    x.b.bc.B_demo = B_demo;
-    x.b.bc.bc_coef = B_demo > 0 ? (float)(2.0 * (double)bc_weight / (double)B_demo) : 0.f;
-    x.b.bc.bc_part = bc_part;
     x.qf.q_demo = q_demo;
     x.qf.keep_part = keep_part;
     return rows_dispatch(r.actor.hp, FAM_ACTOR_BCQ, 0, 0, &x, 1, r.B, S(stream));
@@ -710,17 +706,19 @@ int nav_td3_pop_table_build(const nav_td3_member* members, int32_t n_members, in
     return rc;
 }
 
-static int rows_pop_launch(const nav_td3_member* members, int32_t n_members, int64_t B,
-                           const void* table, int64_t size, uint32_t counter, int32_t split_twins,
-                           int fam, void* stream) {
+// the three population row launches; bc: the BC form's members (its table is the BC table)
+static int rows_pop_launch(const nav_td3_member* members, const nav_td3_member_bc* bc,
+                           int32_t n_members, int64_t B, const void* table, int64_t size,
+                           uint32_t counter, int32_t split_twins, int fam, void* stream) {
     if (!table) return NAV_EINVAL;
-    const int rc = td3_pop_check(members, n_members, B, nullptr, nullptr);
+    const int rc = fam == FAM_ACTOR_BC_POP
+        ? td3_pop_bc_check(members, bc, n_members, B, table, nullptr, nullptr)
+        : td3_pop_check(members, n_members, B, nullptr, nullptr);
     if (rc) return rc;
-    if (size < 1 || size > members[0].replay.capacity || size > ((int64_t)1 << 32))
-        return NAV_EINVAL;
+    if (!fill_ok(size, members[0].replay.capacity)) return NAV_EINVAL;
     RowsPopLaunch a{};
     const char* t = static_cast<const char*>(table);
-    a.k.table = fam == FAM_CRITIC_POP ? t : t + (size_t)n_members * sizeof(CriticRowsArgs);
+    a.k.table = fam == FAM_ACTOR_POP ? t + (size_t)n_members * sizeof(CriticRowsArgs) : t;
     a.k.size = size;
     a.k.counter = counter;
     a.k.split_twins = split_twins;
@@ -736,12 +734,14 @@ int nav_td3_critic_rows_pop(const nav_td3_member* members, int32_t n_members, in
     // the twins in separate workgroups while all members' rows leave CUs idle, as
     // nav_td3_critic_rows chooses for one member
     const int tw = split_twins < 0 ? ((int64_t)n_members * B <= 2048 ? 1 : 0) : (split_twins ? 1 : 0);
-    return rows_pop_launch(members, n_members, B, table, size, counter, tw, FAM_CRITIC_POP, stream);
+    return rows_pop_launch(members, nullptr, n_members, B, table, size, counter, tw, FAM_CRITIC_POP,
+                           stream);
 }
 
 int nav_td3_actor_rows_pop(const nav_td3_member* members, int32_t n_members, int64_t B,
                            const void* table, int64_t size, uint32_t counter, void* stream) {
-    return rows_pop_launch(members, n_members, B, table, size, counter, 0, FAM_ACTOR_POP, stream);
+    return rows_pop_launch(members, nullptr, n_members, B, table, size, counter, 0, FAM_ACTOR_POP,
+                           stream);
 }
 
 int64_t nav_td3_pop_bc_table_bytes(int32_t n_members) {
@@ -771,7 +771,7 @@ int nav_td3_mix_idx_pop(const nav_td3_member* members, const nav_td3_member_bc* 
                         uint32_t counter, int32_t actor_too, void* stream) {
     const int rc = td3_pop_bc_check(members, bc, n_members, B, bc_table, nullptr, nullptr);
     if (rc) return rc;
-    if (!pop_size_ok(members, size)) return NAV_EINVAL;
+    if (!fill_ok(size, members[0].replay.capacity)) return NAV_EINVAL;
     return navi_mix_idx_pop_launch(
         static_cast<const char*>(bc_table) + (size_t)n_members * sizeof(ActorRowsBcArgs),
         n_members, B, size, members[0].replay.capacity, counter, actor_too, S(stream));
@@ -780,22 +780,12 @@ int nav_td3_mix_idx_pop(const nav_td3_member* members, const nav_td3_member_bc* 
 int nav_td3_actor_rows_bc_pop(const nav_td3_member* members, const nav_td3_member_bc* bc,
                               int32_t n_members, int64_t B, const void* bc_table, int64_t size,
                               uint32_t counter, void* stream) {
-    const int rc = td3_pop_bc_check(members, bc, n_members, B, bc_table, nullptr, nullptr);
-    if (rc) return rc;
-    if (!pop_size_ok(members, size)) return NAV_EINVAL;
-    RowsPopLaunch a{};
-    a.k.table = bc_table;
-    a.k.size = size;
-    a.k.counter = counter;
-    a.B = B;
-    a.n_hidden = members[0].critics[0].n_hidden;
-    a.n_members = n_members;
-    return rows_dispatch(members[0].actor.hidden_pad, FAM_ACTOR_BC_POP, 0, 0, &a, 1, B, S(stream));
+    return rows_pop_launch(members, bc, n_members, B, bc_table, size, counter, 0, FAM_ACTOR_BC_POP,
+                           stream);
 }
 
 int64_t nav_mlp_mask_count(int32_t hidden_pad, int32_t n_hidden, int64_t M) {
-    if (hidden_pad < 32 || hidden_pad > 256 || (hidden_pad & 31) || n_hidden < 1 || M < 0)
-        return NAV_EINVAL;
+    if (!width_ok(hidden_pad) || n_hidden < 1 || M < 0) return NAV_EINVAL;
     return (int64_t)n_hidden * mask_rowtiles(M) * (hidden_pad / 32) * 64;
 }
 

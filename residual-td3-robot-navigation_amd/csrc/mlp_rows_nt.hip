@@ -52,98 +52,84 @@ void launch_bwd(const BwdArgs& a, int n_nets, hipStream_t st) {
              a);
 }
 
-// critic_rows and actor_rows: the critics' row-backward form is 1 also for 2 hidden layers (its
-// gemm_cols loop then runs no layer): the form-2 instantiation came out at 286 registers (one
-// workgroup per CU), form 1 at 236
-template <int NT, int RT>
-void launch_critic_rows(const CriticRowsArgs& a, hipStream_t st) {
-    constexpr int TM = RT * 32;
-    auto k = a.critic[0].n_hidden == 1 ? k_td3_critic_rows<NT, RT, 0> : k_td3_critic_rows<NT, RT, 1>;
-    const unsigned gx = row_blocks(a.B, TM), gy = a.split_twins ? 2u : 1u;
-    CriticRowsArgs w = a;
+// The warmed single-learner row programs (critic_rows, actor_rows and their forms) launch in one
+// place: the instantiation by the critic's depth (k_one: one hidden layer), B rows' blocks x gy
+// compute workgroups with the L2 warmer rows of `nets` on top, `lds` bytes of LDS. `w` is the
+// launcher's own copy of the arguments and `warm` the WarmList embedded in it.
+template <typename A>
+void launch_warmed(void (*k_one)(A), void (*k_more)(A), int n_hidden, A& w, WarmList& warm,
+                   int64_t B, int tm, unsigned gy, const WarmNet* nets, int n, size_t lds,
+                   hipStream_t st) {
+    const unsigned gx = row_blocks(B, tm);
+    const unsigned wy = set_warmers(warm, nets, n, gx, gy);
+    launch_k(n_hidden == 1 ? k_one : k_more, dim3(gx, gy + wy), lds, st, w);
+}
+
+// critic_rows and its weighted form (`r`: the plain arguments inside `w`). The critics'
+// row-backward form is 1 also for 2 hidden layers (its gemm_cols loop then runs no layer): the
+// form-2 instantiation came out at 286 registers (one workgroup per CU), form 1 at 236
+template <int NT, int RT, typename A>
+void launch_critic(void (*k_one)(A), void (*k_more)(A), A& w, CriticRowsArgs& r, hipStream_t st) {
     // (the targets: forward only)
-    const WarmNet nets[] = {{a.actor_t, true}, {a.critic_t[0], true}, {a.critic_t[1], true},
-                            {a.critic[0], false}, {a.critic[1], false}};
-    const unsigned wy = set_warmers(w.warm, nets, 5, gx, gy);
-    launch_k(k, dim3(gx, gy + wy), critic_rows_lds(TM, NT * 32), st, w);
+    const WarmNet nets[] = {{r.actor_t, true}, {r.critic_t[0], true}, {r.critic_t[1], true},
+                            {r.critic[0], false}, {r.critic[1], false}};
+    launch_warmed(k_one, k_more, r.critic[0].n_hidden, w, r.warm, r.B, RT * 32,
+                  r.split_twins ? 2u : 1u, nets, 5, critic_rows_lds(RT * 32, NT * 32), st);
 }
 
 template <int NT, int RT>
-void launch_actor_rows(const ActorRowsArgs& a, hipStream_t st) {
-    constexpr int TM = RT * 32;
-    auto k = a.critic.n_hidden == 1 ? k_td3_actor_rows<NT, RT, 0> : k_td3_actor_rows<NT, RT, 1>;
-    const unsigned gx = row_blocks(a.B, TM);
-    ActorRowsArgs w = a;
-    const WarmNet nets[] = {{a.actor, false}, {a.critic, false}};
-    const unsigned wy = set_warmers(w.warm, nets, 2, gx, 1u);
-    launch_k(k, dim3(gx, 1u + wy), actor_rows_lds(TM, NT * 32), st, w);
+void launch_critic_rows(CriticRowsArgs w, hipStream_t st) {
+    launch_critic<NT, RT>(k_td3_critic_rows<NT, RT, 0>, k_td3_critic_rows<NT, RT, 1>, w, w, st);
 }
 
 // the weighted form (prioritised replay): the plain form's grid, warmers and LDS
 template <int NT, int RT>
-void launch_critic_rows_w(const CriticRowsWArgs& a, hipStream_t st) {
-    constexpr int TM = RT * 32;
-    auto k = a.r.critic[0].n_hidden == 1 ? k_td3_critic_rows_w<NT, RT, 0>
-                                         : k_td3_critic_rows_w<NT, RT, 1>;
-    const unsigned gx = row_blocks(a.r.B, TM), gy = a.r.split_twins ? 2u : 1u;
-    CriticRowsWArgs w = a;
-    const WarmNet nets[] = {{a.r.actor_t, true}, {a.r.critic_t[0], true}, {a.r.critic_t[1], true},
-                            {a.r.critic[0], false}, {a.r.critic[1], false}};
-    const unsigned wy = set_warmers(w.r.warm, nets, 5, gx, gy);
-    launch_k(k, dim3(gx, gy + wy), critic_rows_lds(TM, NT * 32), st, w);
+void launch_critic_rows_w(CriticRowsWArgs w, hipStream_t st) {
+    launch_critic<NT, RT>(k_td3_critic_rows_w<NT, RT, 0>, k_td3_critic_rows_w<NT, RT, 1>, w, w.r,
+                          st);
 }
 
-// the BC forms; bc_only warms the actor's images alone
+// actor_rows and its BC forms (`r`: the plain arguments inside `w`): the actor's images warmed
+// and, with n_warm 2, the critic's
+template <int RT, typename A>
+void launch_actor(void (*k_one)(A), void (*k_more)(A), A& w, ActorRowsArgs& r, int n_warm,
+                  size_t lds, hipStream_t st) {
+    const WarmNet nets[] = {{r.actor, false}, {r.critic, false}};
+    launch_warmed(k_one, k_more, r.critic.n_hidden, w, r.warm, r.B, RT * 32, 1u, nets, n_warm, lds,
+                  st);
+}
+
 template <int NT, int RT>
-void launch_actor_rows_bc(const ActorRowsBcArgs& a, hipStream_t st) {
-    constexpr int TM = RT * 32;
-    auto k = a.bc_only                ? k_td3_actor_rows_bc<NT, RT, 1, ACTOR_BC_ONLY>
-             : a.r.critic.n_hidden == 1 ? k_td3_actor_rows_bc<NT, RT, 0, ACTOR_TD3_BC>
-                                        : k_td3_actor_rows_bc<NT, RT, 1, ACTOR_TD3_BC>;
-    const unsigned gx = row_blocks(a.r.B, TM);
-    ActorRowsBcArgs w = a;
-    const WarmNet nets[] = {{a.r.actor, false}, {a.r.critic, false}};
-    const unsigned wy = set_warmers(w.r.warm, nets, a.bc_only ? 1 : 2, gx, 1u);
-    launch_k(k, dim3(gx, 1u + wy), actor_rows_bc_lds(TM, NT * 32), st, w);
+void launch_actor_rows(ActorRowsArgs w, hipStream_t st) {
+    launch_actor<RT>(k_td3_actor_rows<NT, RT, 0>, k_td3_actor_rows<NT, RT, 1>, w, w, 2,
+                     actor_rows_lds(RT * 32, NT * 32), st);
+}
+
+// the BC forms; bc_only runs no critic pass: CBM 1 at every depth, the actor's images alone warmed
+template <int NT, int RT>
+void launch_actor_rows_bc(ActorRowsBcArgs w, hipStream_t st) {
+    constexpr size_t lds = actor_rows_bc_lds(RT * 32, NT * 32);
+    if (w.bc_only)
+        launch_actor<RT>(k_td3_actor_rows_bc<NT, RT, 1, ACTOR_BC_ONLY>,
+                         k_td3_actor_rows_bc<NT, RT, 1, ACTOR_BC_ONLY>, w, w.r, 1, lds, st);
+    else
+        launch_actor<RT>(k_td3_actor_rows_bc<NT, RT, 0, ACTOR_TD3_BC>,
+                         k_td3_actor_rows_bc<NT, RT, 1, ACTOR_TD3_BC>, w, w.r, 2, lds, st);
 }
 
 // the Q-filtered BC form: the BC form's grid and warmers, its LDS and the rows' Q1(s, a_demo)
 template <int NT, int RT>
-void launch_actor_rows_bcq(const ActorRowsBcqArgs& a, hipStream_t st) {
-    constexpr int TM = RT * 32;
-    auto k = a.b.r.critic.n_hidden == 1 ? k_td3_actor_rows_bcq<NT, RT, 0>
-                                        : k_td3_actor_rows_bcq<NT, RT, 1>;
-    const unsigned gx = row_blocks(a.b.r.B, TM);
-    ActorRowsBcqArgs w = a;
-    const WarmNet nets[] = {{a.b.r.actor, false}, {a.b.r.critic, false}};
-    const unsigned wy = set_warmers(w.b.r.warm, nets, 2, gx, 1u);
-    launch_k(k, dim3(gx, 1u + wy), actor_rows_bcq_lds(TM, NT * 32), st, w);
+void launch_actor_rows_bcq(ActorRowsBcqArgs w, hipStream_t st) {
+    launch_actor<RT>(k_td3_actor_rows_bcq<NT, RT, 0>, k_td3_actor_rows_bcq<NT, RT, 1>, w, w.b.r, 2,
+                     actor_rows_bcq_lds(RT * 32, NT * 32), st);
 }
 
-// the population forms: grid.z = the member, no L2 warmer rows
-template <int NT, int RT>
-void launch_critic_rows_pop(const RowsPopLaunch& a, hipStream_t st) {
-    constexpr int TM = RT * 32;
-    auto k = a.n_hidden == 1 ? k_td3_critic_rows_pop<NT, RT, 0> : k_td3_critic_rows_pop<NT, RT, 1>;
-    launch_k(k, dim3(row_blocks(a.B, TM), a.k.split_twins ? 2u : 1u, (unsigned)a.n_members),
-             critic_rows_lds(TM, NT * 32), st, a.k);
-}
-
-template <int NT, int RT>
-void launch_actor_rows_pop(const RowsPopLaunch& a, hipStream_t st) {
-    constexpr int TM = RT * 32;
-    auto k = a.n_hidden == 1 ? k_td3_actor_rows_pop<NT, RT, 0> : k_td3_actor_rows_pop<NT, RT, 1>;
-    launch_k(k, dim3(row_blocks(a.B, TM), 1u, (unsigned)a.n_members), actor_rows_lds(TM, NT * 32),
-             st, a.k);
-}
-
-// the population's BC form: the BC kernel's LDS, the population forms' grid
-template <int NT, int RT>
-void launch_actor_rows_bc_pop(const RowsPopLaunch& a, hipStream_t st) {
-    constexpr int TM = RT * 32;
-    auto k = a.n_hidden == 1 ? k_td3_actor_rows_bc_pop<NT, RT, 0> : k_td3_actor_rows_bc_pop<NT, RT, 1>;
-    launch_k(k, dim3(row_blocks(a.B, TM), 1u, (unsigned)a.n_members),
-             actor_rows_bc_lds(TM, NT * 32), st, a.k);
+// the population forms (the three launches are in rows_rt): grid.z = the member, no L2 warmer rows
+template <int RT>
+void launch_pop(void (*k_one)(RowsPop), void (*k_more)(RowsPop), const RowsPopLaunch& a,
+                unsigned gy, size_t lds, hipStream_t st) {
+    launch_k(a.n_hidden == 1 ? k_one : k_more,
+             dim3(row_blocks(a.B, RT * 32), gy, (unsigned)a.n_members), lds, st, a.k);
 }
 
 template <int NT, int RT, bool POP>
@@ -164,14 +150,18 @@ int rows_rt(int fam, int in_mode, int out_mode, const void* args, int n_nets, hi
         launch_critic_rows_w<NT, RT>(*static_cast<const CriticRowsWArgs*>(args), st);
     } else if constexpr (ROLE == ROLE_BC) {
         launch_actor_rows_bc<NT, RT>(*static_cast<const ActorRowsBcArgs*>(args), st);
-    } else if constexpr (ROLE == ROLE_BCPOP) {
-        launch_actor_rows_bc_pop<NT, RT>(*static_cast<const RowsPopLaunch*>(args), st);
+    } else if constexpr (ROLE == ROLE_BCPOP) {  // the BC kernel's LDS, the population's grid
+        launch_pop<RT>(k_td3_actor_rows_bc_pop<NT, RT, 0>, k_td3_actor_rows_bc_pop<NT, RT, 1>,
+                       *static_cast<const RowsPopLaunch*>(args), 1u,
+                       actor_rows_bc_lds(RT * 32, NT * 32), st);
     } else if constexpr (ROLE == ROLE_LPOP) {
         const RowsPopLaunch& a = *static_cast<const RowsPopLaunch*>(args);
         if (fam == FAM_CRITIC_POP)
-            launch_critic_rows_pop<NT, RT>(a, st);
+            launch_pop<RT>(k_td3_critic_rows_pop<NT, RT, 0>, k_td3_critic_rows_pop<NT, RT, 1>, a,
+                           a.k.split_twins ? 2u : 1u, critic_rows_lds(RT * 32, NT * 32), st);
         else
-            launch_actor_rows_pop<NT, RT>(a, st);
+            launch_pop<RT>(k_td3_actor_rows_pop<NT, RT, 0>, k_td3_actor_rows_pop<NT, RT, 1>, a,
+                           1u, actor_rows_lds(RT * 32, NT * 32), st);
     } else if constexpr (ROLE == ROLE_POP) {
         if (fam == FAM_TEST_POP) {
             launch_test<NT, RT, true>(*static_cast<const TestArgs*>(args), st);

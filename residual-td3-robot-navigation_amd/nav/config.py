@@ -100,6 +100,53 @@ class TD3Config:
     n_step: int = 1
     net: NetConfig = field(default_factory=NetConfig)
 
+    def bc_on(self):
+        # (bc_q_filter alone counts as on, so that b_demo() refuses it)
+        return self.demo_fraction != 0 or self.bc_weight != 0 or self.bc_q_filter
+
+    def per_on(self):
+        return self.per_alpha != 0
+
+    def nstep_on(self):
+        return self.n_step > 1
+
+    # ---- the rule table: every refusal of a mode or of a combination of modes, stated once
+    def _rules(self, grad_hook=None, overlap_collect=False, population=None):
+        """(refused, message) row by row, the ranges first; a generator, so a row is evaluated
+        only once the rows before it have passed."""
+        yield (not isinstance(self.n_step, int) or not 1 <= self.n_step <= NSTEP_MAX,
+               f"n_step must be an int in 1 .. {NSTEP_MAX} (1 = multi-step returns off)")
+        yield (self.per_alpha < 0 or self.per_alpha != self.per_alpha,
+               "per_alpha must be >= 0 (0 = prioritised replay off)")
+        # (mode, on, its verbs, its clash with the demonstrations: for PER a bare filter too)
+        modes = (("multi-step returns (n_step > 1)", self.nstep_on(), "are", "do",
+                  self.demo_fraction != 0 or self.bc_weight != 0),
+                 ("prioritised replay (per_alpha > 0)", self.per_on(), "is", "does", self.bc_on()))
+        for name, on, be, _, _ in modes[::-1]:
+            yield population and on, f"{name} {be} not available to population members"
+        yield (population == "batched" and self.bc_q_filter, 'bc_q_filter is not available with '
+               'learner="batched" (no population form of the Q-filtered actor kernel)')
+        for name, on, _, do, demos in modes:
+            yield on and demos, f"{name} {do} not combine with demo_fraction / bc_weight"
+            yield (on and grad_hook is not None,
+                   f"{name} {do} not combine with a grad_hook (shared policy)")
+            yield on and overlap_collect, f"{name} {do} not combine with overlap_collect"
+
+    def check(self, grad_hook=None, overlap_collect=False, population=None, member=None):
+        """ValueError for a mode field out of range or a combination that is not built: the rule
+        table, then b_demo()'s rules. grad_hook / overlap_collect: what the learner or trainer
+        runs with; population: None or PopulationTrainer's learner= ("members", "batched"), with
+        `member` the index the message names. Needs no device and no library."""
+        for refused, text in self._rules(grad_hook, overlap_collect, population):
+            if refused:
+                raise ValueError(text if member is None else f"{text}: member {member}")
+        try:
+            self.b_demo()
+        except ValueError as e:
+            if member is None:
+                raise
+            raise ValueError(f"member {member}: {e}") from None
+
     def b_demo(self):
         """Demonstration rows per batch, round(demo_fraction * batch_size); ValueError for a
         demo_fraction outside [0, 1], a bc_weight without such rows, or bc_q_filter without the
@@ -118,13 +165,29 @@ class TD3Config:
     def check_n_step(self, grad_hook=None):
         """ValueError for an n_step outside 1 .. NAV_NSTEP_MAX, or n_step > 1 with what
         multi-step returns do not combine with (needs no device)."""
-        if not isinstance(self.n_step, int) or not 1 <= self.n_step <= NSTEP_MAX:
-            raise ValueError(f"n_step must be an int in 1 .. {NSTEP_MAX} (1 = multi-step "
-                             "returns off)")
-        if self.n_step > 1:
-            if self.demo_fraction != 0 or self.bc_weight != 0:
-                raise ValueError("multi-step returns (n_step > 1) do not combine with "
-                                 "demo_fraction / bc_weight")
-            if grad_hook is not None:
-                raise ValueError("multi-step returns (n_step > 1) do not combine with a "
-                                 "grad_hook (shared policy)")
+        for refused, text in self._rules(grad_hook):  # the table's rows that name n_step
+            if refused and "n_step" in text:
+                raise ValueError(text)
+
+
+# the mode fields, listed once: VecTrainer's keywords, a checkpoint's meta, tools/evaluate.py
+MODE_FIELDS = ("demo_fraction", "bc_weight", "q_weight", "bc_q_filter", "per_alpha", "per_beta",
+               "per_eps", "n_step")
+
+
+def mode_meta(cfg):
+    """A checkpoint meta's mode keys: the demonstration weights always, a later mode's fields
+    only while it is on (a run without them writes the keys it wrote before they existed)."""
+    per = cfg.per_on()
+    on = dict(per_alpha=per, per_beta=per, per_eps=per, n_step=cfg.nstep_on(),
+              bc_q_filter=cfg.bc_q_filter)
+    return {k: getattr(cfg, k) for k in MODE_FIELDS if on.get(k, True)}
+
+
+def mode_kwargs(given):
+    """TD3Config's mode fields from VecTrainer's keywords or a checkpoint's meta (other keys
+    ignored), a missing one at its default; floats and the flag cast, n_step left to check()."""
+    d = TD3Config()
+    cast = {float: float, bool: bool}
+    return {k: cast.get(type(getattr(d, k)), lambda v: v)(given.get(k, getattr(d, k)))
+            for k in MODE_FIELDS}

@@ -302,11 +302,9 @@ class PopulationLearner:
         """(Re)build the device table from the members' present buffers and hyper-parameters; each
         member's workspace is (re)allocated for the population's split counts first."""
         self._check_schedule()
-        for t in self.td3:
-            if t._B != self.B or (t.splits_c, t.splits_a) != self.wgrad_splits:
-                t.wgrad_splits = self.wgrad_splits
-                t._B = 0
-                t._workspace(self.B)
+        for t in self.td3:  # (a workspace that has them already stays)
+            t.wgrad_splits = self.wgrad_splits
+            t._workspace(self.B)
         inject, bc = self._inject, self._bc_members()
         if bc is not None:
             # every member's indices come from its idx_c / idx_a, which the mix launch fills; an
@@ -338,10 +336,9 @@ class PopulationLearner:
         """The members' nav_td3_member_bc entries (index pointers still unset), or None if no
         member learns from demonstrations. A member with it off takes B_demo = 0, bc_weight = 0
         and q_weight = 1: the plain actor loss, bit for bit."""
-        for m, t in enumerate(self.td3):
-            if t.cfg.bc_q_filter:
-                raise ValueError("PopulationLearner: bc_q_filter has no population form of the "
-                                 f"actor kernel (member {m}): take the per-member path")
+        for m, (t, ring) in enumerate(zip(self.td3, self.rings)):  # (built from bare TD3s too)
+            t.cfg.check(population="batched", member=m)
+            ring.check_serves(t.cfg)
         if not any(t.bc_on() for t in self.td3):
             return None
         out = []
@@ -349,8 +346,6 @@ class PopulationLearner:
             b = NavTd3MemberBc()
             b.B_demo = t.b_demo() if t.bc_on() else 0
             b.n_demo = int(ring.tail.shape[0])
-            if b.B_demo and b.n_demo < 1:
-                raise ValueError("demo_fraction > 0 needs a replay ring with a demonstration tail")
             b.q_weight, b.bc_weight = (t.cfg.q_weight, t.cfg.bc_weight) if t.bc_on() else (1.0, 0.0)
             b.bc_part = t.bc_part.data_ptr()
             out.append(b)
@@ -432,33 +427,20 @@ class PopulationTrainer:
             raise ValueError('learner="batched" issues one launch for all members: streams must '
                              'be 1')
         routed = [route_overrides(m) for m in self.members]
-        for m, (_, ck, _) in enumerate(routed):
-            if ck.get("per_alpha", 0.0) != 0:
-                raise ValueError("prioritised replay (per_alpha > 0) is not available to "
-                                 f"population members: member {m}")
-            if ck.get("n_step", 1) != 1:
-                raise ValueError("multi-step returns (n_step > 1) are not available to "
-                                 f"population members: member {m}")
-            # the BC term's Q-filter: each member's own launches run it (learner="members"); the
-            # one-launch learner has no population form of that kernel
-            if ck.get("bc_q_filter", False):
-                if learner == "batched":
-                    raise ValueError('bc_q_filter is not available with learner="batched" (no '
-                                     'population form of the Q-filtered actor kernel): member '
-                                     f'{m}')
-                try:  # without the BC term it filters: refused as TD3Config.b_demo refuses it
-                    K.TD3Config(batch_size=int(batch), bc_q_filter=True,
-                                **{k: ck[k] for k in BC_KEYS if k in ck}).b_demo()
-                except ValueError as e:
-                    raise ValueError(f"member {m}: {e}") from None
-        # learning from the demonstrations: on for a member whose demo_fraction or bc_weight is
-        # non-zero (TD3.bc_on); then every member's ring carries a tail of its own envs'
-        # demonstrations
-        self.bc = any(ck.get("demo_fraction", 0.0) != 0 or ck.get("bc_weight", 0.0) != 0
-                      for _, ck, _ in routed)
         if not demos and any(k in ck for _, ck, _ in routed for k in BC_KEYS):
             raise ValueError("demo_fraction / bc_weight / q_weight need demonstrations: "
                              "demos=True")
+        # each member's config, and everything it refuses (the modes without a population form,
+        # the BC term's Q-filter with the one-launch learner), before anything is built
+        cfgs = [K.TD3Config(batch_size=int(batch), num_epochs=int(updates_per_step),
+                            net=K.NetConfig(hidden=hidden, n_hidden=n_hidden), **ck)
+                for _, ck, _ in routed]
+        for m, cfg in enumerate(cfgs):
+            cfg.check(population=learner, member=m)
+        # learning from the demonstrations: on for a member whose demo_fraction or bc_weight is
+        # non-zero (TD3.bc_on); then every member's ring carries a tail of its own envs'
+        # demonstrations
+        self.bc = any(cfg.bc_on() for cfg in cfgs)
         self.epm = int(envs_per_member)
         if self.bc:  # members own whole env groups (ValueError otherwise)
             member_demo_groups(0, self.epm, int(envs_per_group) if envs_per_group else self.epm)
@@ -492,14 +474,10 @@ class PopulationTrainer:
         # batched run bit for bit)
         if learner == "batched":
             wgrad_splits = PopulationLearner.split_counts(P, hidden, n_hidden, int(batch))
-        for m, (pk, ck, ex) in enumerate(routed):
-            cfg = K.TD3Config(batch_size=int(batch), num_epochs=int(updates_per_step),
-                              net=K.NetConfig(hidden=hidden, n_hidden=n_hidden), **ck)
+        for m, ((pk, _, ex), cfg) in enumerate(zip(routed, cfgs)):
             t = TD3(cfg, device=self.device, seed=int(ex.get("seed", self.seed)),
                     wgrad_splits=wgrad_splits)
             t._workspace(cfg.batch_size)  # allocated now, on the stream every later one waits for
-            if t.bc_on():
-                t.b_demo()  # validates demo_fraction / bc_weight against the batch size
             self.td3.append(t)
             sl = self.member_slice(m)
             if "initial_noise" in ex:
@@ -700,10 +678,7 @@ class PopulationTrainer:
         # then, so only a lower bound above 0 could lift it): refused as TD3.b_demo refuses it
         if explore and float(explore.get("bc_weight", (0.0, 0.0))[0]) > 0:
             for s in src:
-                c = self.td3[s].cfg
-                if int(round(c.demo_fraction * c.batch_size)) == 0:
-                    raise ValueError("bc_weight needs demonstration rows in the batch: member "
-                                     f"{s}'s demo_fraction * batch_size rounds to 0")
+                dataclasses.replace(self.td3[s].cfg, bc_weight=1.0).check(member=s)
         if not src:
             return []
         if explore and rng is None:

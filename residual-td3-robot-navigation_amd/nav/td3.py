@@ -63,10 +63,22 @@ class TD3:
                  critic2=None, grad_hook=None, wgrad_splits=None):
         self.cfg = cfg or K.TD3Config()
         c = self.cfg
-        # multi-step returns (cfg.n_step > 1; off by default): what it does not combine with is
-        # refused before anything is allocated
-        self.nstep_launches = 0  # nav_nstep_rows calls issued (0 with the feature off)
-        c.check_n_step(grad_hook)
+        # every mode's refusals (TD3Config.check) and the hook's contract, before anything is
+        # allocated; _static checks again once a mode field has changed
+        c.check(grad_hook)
+        self._checked = self._modes()
+        # shared policy (BASELINE config 5): grad_hook(bucket) SUM-all-reduces a flat gradient
+        # bucket in place (nav.dist.GradAllReduce: RCCL over xGMI) and Adam divides by the hook's
+        # world_size. The contract is explicit: a hook without world_size is refused, since a
+        # plain SUM callable would silently train on world_size x the mean gradient.
+        self.grad_hook = grad_hook
+        self.grad_div = 1.0
+        if grad_hook is not None:
+            ws = getattr(grad_hook, "world_size", None)
+            if not isinstance(ws, int) or ws < 1:
+                raise ValueError("grad_hook must carry an int world_size >= 1: it SUM-all-reduces "
+                                 "the gradient bucket and Adam divides by world_size")
+            self.grad_div = float(ws)
         nc = c.net
         self.device = torch.device(device)
         mk = lambda di, do: DeviceMLP(di, do, nc.hidden, nc.n_hidden, self.device)  # noqa: E731
@@ -88,37 +100,16 @@ class TD3:
         self.mix_launches = 0    # nav_td3_mix_idx launches issued (0 with the feature off)
         self._bc_ws = None       # bc_loss's workspace, by row count
         self._last_b_demo = 0    # demonstration rows of the last BC launch (bc_loss_value)
-        # shared policy (BASELINE config 5): grad_hook(bucket) SUM-all-reduces a flat gradient
-        # bucket in place (nav.dist.GradAllReduce: RCCL over xGMI) and Adam divides by the hook's
-        # world_size. The contract is explicit: a hook without world_size is refused, since a
-        # plain SUM callable would silently train on world_size x the mean gradient.
-        self.grad_hook = grad_hook
-        self.grad_div = 1.0
-        if grad_hook is not None:
-            ws = getattr(grad_hook, "world_size", None)
-            if not isinstance(ws, int) or ws < 1:
-                raise ValueError("grad_hook must carry an int world_size >= 1: it SUM-all-reduces "
-                                 "the gradient bucket and Adam divides by world_size")
-            self.grad_div = float(ws)
-        # prioritised replay (cfg.per_alpha > 0; off by default): what it does not combine with
-        # is refused here
+        # prioritised replay (cfg.per_alpha > 0) and multi-step returns (cfg.n_step > 1)
         self.per_launches = 0    # nav_per_* calls issued (0 with the feature off)
-        if c.per_alpha < 0 or c.per_alpha != c.per_alpha:
-            raise ValueError("per_alpha must be >= 0 (0 = prioritised replay off)")
-        if self.per_on():
-            if self.bc_on():
-                raise ValueError("prioritised replay (per_alpha > 0) does not combine with "
-                                 "demo_fraction / bc_weight")
-            if grad_hook is not None:
-                raise ValueError("prioritised replay (per_alpha > 0) does not combine with a "
-                                 "grad_hook (shared policy)")
+        self.nstep_launches = 0  # nav_nstep_rows calls issued (0 with the feature off)
         # row splits of the weight-gradient launches, (critic twins, actor); None = as many as
         # fill the chip (nav_mlp_wgrad_splits; tuning only)
         self.wgrad_splits = wgrad_splits
         # the twin online critics in separate workgroups: -1 = the library's choice by batch size
         # (1 / 0 force either form; the results are bit-identical)
         self.split_twins = -1
-        self._B = 0
+        self._B, self._ws_key = 0, None  # the workspace's batch size and key (_workspace)
         # every launch's constant ctypes arguments and work counts (_static), rebuilt when the
         # batch size, the seed or a hyper-parameter they carry changes (its key)
         self._st = None
@@ -128,13 +119,23 @@ class TD3:
         self._ready, self._ready_recorded = None, False
         self.actor_losses, self.critic_losses = [], []
 
-    # ---- workspace, sized per batch
+    def _modes(self):
+        return tuple(getattr(self.cfg, k) for k in K.MODE_FIELDS)
+
+    # ---- workspace, keyed by all it allocates for: batch size, PER, n-step, the split counts
     def _workspace(self, B):
-        if B == self._B:
-            return
         d, hp, nh = self.device, self.actor_network.hp, self.actor_network.n_hidden
-        f = lambda *s: torch.zeros(*s, dtype=torch.float32, device=d)  # noqa: E731
         L = lib()
+        # row splits of the weight-gradient launch (partial slabs): critic twins and actor
+        # separately, as many as fill the chip (wgrad_splits overrides; tuning only)
+        sc = L.nav_mlp_wgrad_splits(2, self.critic_network_1.d_out, hp, nh, B)
+        sa = L.nav_mlp_wgrad_splits(1, self.actor_network.d_out, hp, nh, B)
+        if self.wgrad_splits:
+            sc, sa = (max(1, min(int(v), max(1, B // 32))) for v in self.wgrad_splits)
+        key = (B, self.per_on(), self.nstep_on(), sc, sa)
+        if key == self._ws_key:
+            return
+        f = lambda *s: torch.zeros(*s, dtype=torch.float32, device=d)  # noqa: E731
         self.batch = f(B, 8)
         self.batch2 = f(B, 8)
         self.q1 = f(B)
@@ -170,12 +171,6 @@ class TD3:
         ec = L.nav_mlp_edge_count(4, 1, hp, nh)
         self.eslab1, self.eslab2 = f(self.nblk, ec), f(self.nblk, ec)
         self.eslab_a = f(self.nblk, L.nav_mlp_edge_count(2, 2, hp, nh))
-        # row splits of the weight-gradient launch (partial slabs): critic twins and actor
-        # separately, as many as fill the chip (wgrad_splits overrides; tuning only)
-        sc = L.nav_mlp_wgrad_splits(2, self.critic_network_1.d_out, hp, nh, B)
-        sa = L.nav_mlp_wgrad_splits(1, self.actor_network.d_out, hp, nh, B)
-        if self.wgrad_splits:
-            sc, sa = (max(1, min(int(v), max(1, B // 32))) for v in self.wgrad_splits)
         self.splits_c, self.splits_a = sc, sa
         hc = max(4, L.nav_mlp_hidden_count(hp, nh))
         self.hslab, self.hslab2 = f(max(sc, sa), hc), f(sc, hc)
@@ -184,7 +179,7 @@ class TD3:
         cc = self.critic_network_1.count
         self.grad_c = f(2 * cc)
         self.grad_c1, self.grad_c2 = self.grad_c[:cc], self.grad_c[cc:]
-        self._B = B
+        self._B, self._ws_key = B, key
         self._st = None
 
     # ---- the launches. Each is issued in one place, with its constant arguments and its work
@@ -226,13 +221,15 @@ class TD3:
     def _static(self):
         c = self.cfg
         B = c.batch_size
-        if B != self._B:
-            self._workspace(B)
         key = (B, self.seed, c.policy_noise, c.noise_clip, c.max_action, c.gamma, c.tau,
                self.split_twins, c.bc_weight, c.q_weight, c.demo_fraction, c.per_alpha, c.n_step,
                c.bc_q_filter)
         if self._st is not None and self._st_key == key:
             return self._st
+        if self._modes() != self._checked:  # a mode switched after construction
+            c.check(self.grad_hook)
+            self._checked = self._modes()
+        self._workspace(B)
         c1, c2, a = self.critic_network_1, self.critic_network_2, self.actor_network
         t1, t2 = self.target_critic_network_1, self.target_critic_network_2
         ta, ca = self.target_actor.desc(), a.desc()
@@ -482,19 +479,17 @@ class TD3:
             return 0.0
         return self.keep_part.sum().item() / n
 
-    # ---- prioritised replay
+    # ---- which modes are on (TD3Config's own)
     def per_on(self):
-        return self.cfg.per_alpha != 0
+        return self.cfg.per_on()
 
-    # ---- multi-step returns
     def nstep_on(self):
-        return self.cfg.n_step > 1
+        return self.cfg.nstep_on()
+
+    def bc_on(self):
+        return self.cfg.bc_on()
 
     # ---- learning from demonstrations
-    def bc_on(self):
-        # (bc_q_filter alone counts as on, so that b_demo() refuses it)
-        return self.cfg.demo_fraction != 0 or self.cfg.bc_weight != 0 or self.cfg.bc_q_filter
-
     def b_demo(self):
         """Demonstration rows per batch: the batch's first round(demo_fraction * B) rows."""
         return self.cfg.b_demo()
@@ -609,27 +604,13 @@ class TD3:
         if len(replay) < 1:
             return
         c, L = self.cfg, lib()
-        bc, per = self.bc_on(), self.per_on()
+        bc, per, nstep = c.bc_on(), c.per_on(), c.nstep_on()
+        if bc or per or nstep:  # the ring carries what the modes read (plain: its rows alone)
+            replay.check_serves(c, injected=bool(idx_fn))
         if bc:
-            b_demo = self.b_demo()
-            n_tail = int(replay.tail.shape[0]) if hasattr(replay, "tail") else 0
-            if b_demo and not idx_fn and n_tail < 1:
-                raise ValueError("demo_fraction > 0 needs a replay ring with a demonstration tail")
+            b_demo, n_tail = c.b_demo(), int(replay.tail.shape[0])
         if per:
-            if getattr(replay, "pri", None) is None:
-                raise ValueError("per_alpha > 0 needs a replay ring with priorities "
-                                 "(ReplayRing(priorities=True))")
             pd = replay.per_ref()
-        nstep = self.nstep_on()
-        if nstep:
-            if getattr(replay, "cut", None) is None:
-                raise ValueError("n_step > 1 needs a replay ring with cut marks "
-                                 "(ReplayRing(cuts=True))")
-            if not getattr(replay, "stride", None):
-                raise ValueError("n_step > 1 needs the ring's stride (ReplayRing.stride: the "
-                                 "rows between an env's consecutive transitions, n_envs)")
-            if getattr(self, "staged", None) is None or self.staged.shape[0] != c.batch_size:
-                self._B = 0  # n_step switched on after the workspace was built
         seed, B = self._static()["seed"], self._B
         s = stream_handle(stream)
         for epoch in range(n):

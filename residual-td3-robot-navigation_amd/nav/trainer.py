@@ -21,7 +21,7 @@ from .cem import cem_group_demo_sets
 from .demo_replay import DemoReplay
 from .fields import make_field_device
 from .td3 import TD3
-from .vec_env import ReplayRing, VecEnv
+from .vec_env import ReplayRing, VecEnv, ring_needs
 
 
 def make_env(n, field, seed, envs_per_group, demos, device):
@@ -61,34 +61,33 @@ class VecTrainer:
     def __init__(self, n_envs=65536, hidden=256, n_hidden=2, batch=32768, updates_per_step=2,
                  replay_capacity=None, seed=K.RANDOM_SEED, envs_per_group=1024, demos=True,
                  device="cuda", field=None, grad_hook=None, fuse_tick=True, overlap_collect=False,
-                 demo_fraction=0.0, bc_weight=0.0, q_weight=1.0, demo_rows=None,
-                 per_alpha=0.0, per_beta=0.4, per_eps=1e-6, n_step=1, bc_q_filter=False):
-        """demo_fraction / bc_weight / q_weight: learning from the demonstrations (TD3Config; off
+                 demo_rows=None, **modes):
+        """**modes: the learner's mode fields (config.MODE_FIELDS; any other keyword is a
+        TypeError), each at TD3Config's default; what does not combine is TD3Config.check's.
+        demo_fraction / bc_weight / q_weight: learning from the demonstrations (TD3Config; off
         by default). With demo_fraction or bc_weight non-zero the CEM demonstrations' transitions
         sit in a tail behind the replay ring and a share of every batch is drawn from it (needs
         demos=True, or demo_rows = (frame-0 rows, frame-1 rows) from a checkpoint).
         bc_q_filter: the Q-filter of the BC term (TD3Config; off by default): a demonstration row
-        is cloned only where critic 1 rates its action above the policy's. Needs bc_weight != 0
-        and demonstration rows in the batch (ValueError); td3.bc_kept_fraction() reports the
-        share of rows the last policy epoch kept.
+        is cloned only where critic 1 rates its action above the policy's;
+        td3.bc_kept_fraction() reports the share of rows the last policy epoch kept.
         per_alpha / per_beta / per_eps: prioritised replay (TD3Config; off at per_alpha == 0).
         On, the ring carries one priority per row, every tick stamps its rows with the running
-        maximum, and batches are drawn in proportion to priority. Not with demo_fraction /
-        bc_weight, a grad_hook or overlap_collect (ValueError).
+        maximum, and batches are drawn in proportion to priority.
         n_step: multi-step returns (TD3Config; off at 1). On, the ring carries one cut mark per
         row, every tick writes its rows' marks from its flags, and the critics' target sums up to
-        n_step rewards along the env's rows (stride n_envs). With per_alpha it combines; not with
-        demo_fraction / bc_weight, a grad_hook or overlap_collect (ValueError)."""
-        # multi-step returns: what they do not combine with is refused before anything is built
-        # (the gather reads rows an overlapped tick may be writing); the learner refuses the rest
-        K.TD3Config(n_step=n_step, demo_fraction=float(demo_fraction),
-                    bc_weight=float(bc_weight)).check_n_step(grad_hook)
-        if bc_q_filter:  # the Q-filter without the BC term it filters: refused here too
-            K.TD3Config(batch_size=int(batch), demo_fraction=float(demo_fraction),
-                        bc_weight=float(bc_weight), bc_q_filter=True).b_demo()
-        if n_step > 1 and overlap_collect:
-            raise ValueError("multi-step returns (n_step > 1) do not combine with "
-                             "overlap_collect")
+        n_step rewards along the env's rows (stride n_envs)."""
+        for k in modes:
+            if k not in K.MODE_FIELDS:
+                raise TypeError(f"VecTrainer() got an unexpected keyword argument {k!r}")
+        # the learner's config, and everything it refuses, before anything is built
+        cfg = K.TD3Config(batch_size=int(batch), num_epochs=int(updates_per_step),
+                          net=K.NetConfig(hidden=hidden, n_hidden=n_hidden),
+                          **K.mode_kwargs(modes))
+        cfg.check(grad_hook, overlap_collect)
+        need = ring_needs(cfg)
+        if need["tail"] and not demos and demo_rows is None:
+            raise ValueError("demo_fraction / bc_weight need demonstrations: demos=True")
         self.n = int(n_envs)
         self.device = torch.device(device)
         self.seed = int(seed)
@@ -97,37 +96,23 @@ class VecTrainer:
         self.field = field
         self.env, self._cem = make_env(self.n, field, self.seed, envs_per_group or self.n, demos,
                                        self.device)
-        cfg = K.TD3Config(batch_size=int(batch), num_epochs=int(updates_per_step),
-                          net=K.NetConfig(hidden=hidden, n_hidden=n_hidden),
-                          bc_weight=float(bc_weight), q_weight=float(q_weight),
-                          demo_fraction=float(demo_fraction), per_alpha=float(per_alpha),
-                          per_beta=float(per_beta), per_eps=float(per_eps), n_step=n_step,
-                          bc_q_filter=bool(bc_q_filter))
-        if cfg.per_alpha != 0 and overlap_collect:
-            raise ValueError("prioritised replay (per_alpha > 0) does not combine with "
-                             "overlap_collect")
         self.td3 = TD3(cfg, device=self.device, seed=self.seed, grad_hook=grad_hook)
         cap = replay_capacity or max(4 * self.n, 2 * int(batch), K.BUFFER_SIZE)
-        # the demonstration transitions: in the ring's tail when the learner draws from them,
-        # else built on the first pretrain_bc / bc_loss (no tail: the ring is what it was)
+        # the ring the config needs. The demonstration transitions: in its tail when the learner
+        # draws from them, else built on the first pretrain_bc / bc_loss (the ring is what it was)
+        tail = 0
+        if need["tail"]:  # a checkpoint's rows, else every transition of the CEM's demonstrations
+            st = self._cem[0] if demo_rows is None else None
+            tail = demo_rows[0].shape[0] if st is None else st.shape[0] * (st.shape[1] - 1)
+        self.replay = ReplayRing(cap, self.device, tail=tail, priorities=need["priorities"],
+                                 cuts=need["cuts"])
+        ring = self.replay if need["tail"] else None
         self.demo_replay = None
-        if self.td3.bc_on():
-            self.td3.b_demo()  # validates demo_fraction / bc_weight against the batch size
-            if demo_rows is not None:
-                self.replay = ReplayRing(cap, self.device, tail=demo_rows[0].shape[0])
-                self.demo_replay = DemoReplay.from_rows(demo_rows[0], demo_rows[1], self.replay)
-            elif self._cem is not None:
-                st, ac, gl = self._cem
-                self.replay = ReplayRing(cap, self.device, tail=st.shape[0] * (st.shape[1] - 1))
-                self.demo_replay = DemoReplay(st, ac, gl, self.env.p, ring=self.replay)
-            else:
-                raise ValueError("demo_fraction / bc_weight need demonstrations: demos=True")
-        else:
-            self.replay = ReplayRing(cap, self.device, priorities=self.td3.per_on(),
-                                     cuts=self.td3.nstep_on())
-            if demo_rows is not None:
-                self.demo_replay = DemoReplay.from_rows(demo_rows[0].to(self.device),
-                                                        demo_rows[1])
+        if demo_rows is not None:
+            self.demo_replay = DemoReplay.from_rows(demo_rows[0].to(self.device), demo_rows[1],
+                                                    ring)
+        elif ring is not None:
+            self.demo_replay = DemoReplay(*self._cem, self.env.p, ring=ring)
         self.replay.stride = self.n  # an env's next transition: n_envs rows on
         self.action = torch.zeros(self.n, 2, dtype=torch.float64, device=self.device)
         self.steps = 0
@@ -249,8 +234,7 @@ class VecTrainer:
                      "hidden": self.td3.actor_network.hidden,
                      "n_hidden": self.td3.actor_network.n_hidden,
                      "batch": self.td3.cfg.batch_size, "updates_per_step": self.updates_per_step,
-                     "steps": self.steps, "demo_fraction": self.td3.cfg.demo_fraction,
-                     "bc_weight": self.td3.cfg.bc_weight, "q_weight": self.td3.cfg.q_weight},
+                     "steps": self.steps, **K.mode_meta(self.td3.cfg)},
             "demo_rows": None if self.demo_replay is None else
             {"rows0": self.demo_replay.rows0.cpu(), "rows1": self.demo_replay.rows1.cpu()},
             "env": {k: getattr(e, k).detach().cpu() for k in self.ENV_STATE},
@@ -261,15 +245,10 @@ class VecTrainer:
                        "size": self.replay.size},
             "td3": self.td3.state_dict(),
         }
-        if self.td3.per_on():  # prioritised replay: its hyper-parameters and the priority store
-            c = self.td3.cfg
-            sd["meta"].update(per_alpha=c.per_alpha, per_beta=c.per_beta, per_eps=c.per_eps)
+        if self.td3.per_on():  # prioritised replay: the priority store
             sd["replay"].update(pri=self.replay.pri.cpu(), stat=self.replay.stat.cpu())
-        if self.td3.nstep_on():  # multi-step returns: the horizon and the cut marks
-            sd["meta"].update(n_step=self.td3.cfg.n_step)
+        if self.td3.nstep_on():  # multi-step returns: the cut marks
             sd["replay"].update(cut=self.replay.cut.cpu())
-        if self.td3.cfg.bc_q_filter:  # the BC term's Q-filter (absent: off)
-            sd["meta"].update(bc_q_filter=True)
         return sd
 
     def load_state_dict(self, sd):
@@ -306,12 +285,8 @@ class VecTrainer:
                 replay_capacity=sd["replay"]["rows"].shape[0], seed=m["seed"],
                 envs_per_group=m["envs_per_group"], demos=False, device=device,
                 field=sd["field"].to(device), grad_hook=grad_hook,
-                demo_fraction=m.get("demo_fraction", 0.0), bc_weight=m.get("bc_weight", 0.0),
-                q_weight=m.get("q_weight", 1.0),
                 demo_rows=None if dr is None else (dr["rows0"], dr["rows1"]),
-                per_alpha=m.get("per_alpha", 0.0), per_beta=m.get("per_beta", 0.4),
-                per_eps=m.get("per_eps", 1e-6), n_step=int(m.get("n_step", 1)),
-                bc_q_filter=bool(m.get("bc_q_filter", False)))
+                **K.mode_kwargs(m))
         t.load_state_dict(sd)
         return t
 

@@ -71,6 +71,12 @@ class DemoIndex:
         return g * self.CELLS + (x * self.res).long() * self.side + (y * self.res).long()
 
 
+def ring_needs(cfg):
+    """What a learner with cfg's modes reads beside the ring's rows, as ReplayRing's keywords
+    (the tail's length is the caller's); ReplayRing.check_serves is the contract's other half."""
+    return {"tail": cfg.bc_on(), "priorities": cfg.per_on(), "cuts": cfg.nstep_on()}
+
+
 class ReplayRing:
     """ReplayBuffer (robot.py:58-124) as a device ring of 32-byte rows
     (s0 s1 a0 a1 r s'0 s'1 done, float32)."""
@@ -113,6 +119,22 @@ class ReplayRing:
         self.stride = None
         if cuts:
             self.cut = torch.zeros(self.capacity, dtype=torch.uint8, device=self.rows.device)
+
+    def check_serves(self, cfg, injected=False):
+        """ValueError unless this ring carries what cfg's modes read (ring_needs), once per
+        update; `injected`: the caller gives the sample indices, demonstration rows among them."""
+        if cfg.bc_on() and cfg.b_demo() and not injected and self.tail.shape[0] < 1:
+            raise ValueError("demo_fraction > 0 needs a replay ring with a demonstration tail")
+        if cfg.per_on() and self.pri is None:
+            raise ValueError("per_alpha > 0 needs a replay ring with priorities "
+                             "(ReplayRing(priorities=True))")
+        if cfg.nstep_on():
+            if self.cut is None:
+                raise ValueError("n_step > 1 needs a replay ring with cut marks "
+                                 "(ReplayRing(cuts=True))")
+            if not self.stride:
+                raise ValueError("n_step > 1 needs the ring's stride (ReplayRing.stride: the "
+                                 "rows between an env's consecutive transitions, n_envs)")
 
     def desc(self):
         return NavReplay(self.rows.data_ptr(), self.capacity)

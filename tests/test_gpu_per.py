@@ -675,3 +675,54 @@ def test_ring_without_priorities_refuses_a_per_learner(nav):
     ring.advance(256)
     with pytest.raises(ValueError, match="priorities"):
         t.td3_update(ring, 1)
+
+
+# ---------------------------------------------------------------- the workspace key
+def _filled_ring():
+    """512 seeded rows with priorities (every row stamped) and cut marks, stride 64."""
+    from nav.vec_env import ReplayRing
+    g = torch.Generator().manual_seed(7)
+    ring = ReplayRing(512, DEV, priorities=True, cuts=True)
+    ring.rows.copy_(torch.randn(512, 8, generator=g))
+    ring.rows[:, 7] = (torch.rand(512, generator=g) < 0.05).float()
+    ring.cut.copy_((torch.rand(512, generator=g) < 0.1).to(torch.uint8))
+    ring.stamp(ring.advance(512), 512)
+    ring.stride = 64
+    return ring
+
+
+def _sd_same(a, b):
+    if isinstance(a, dict):
+        return set(a) == set(b) and all(_sd_same(a[k], b[k]) for k in a)
+    return torch.equal(a, b) if torch.is_tensor(a) else a == b
+
+
+@pytest.mark.parametrize("field,value", [("per_alpha", 0.6), ("n_step", 3)])
+def test_a_mode_switched_on_later_gets_its_workspace(nav, field, value):
+    """The workspace is keyed by what it allocates for. A: a learner built with the mode off runs
+    2 epochs, has the mode switched on in its config and runs 2 more. B: a learner built with the
+    mode on takes A's state and ring priorities of that moment and runs 2 epochs. Equal state
+    and equal ring priorities, bit for bit."""
+    from nav import config as K
+    from nav.td3 import TD3
+    cfg = lambda **kw: K.TD3Config(batch_size=64, net=K.NetConfig(hidden=64, n_hidden=2),  # noqa: E731
+                                   **kw)
+    ring_a, ring_b = _filled_ring(), _filled_ring()
+    a = TD3(cfg(), device=DEV)
+    a.td3_update(ring_a, 2)
+    assert not hasattr(a, "w_per") and not hasattr(a, "staged")
+    torch.cuda.synchronize()
+    mid = a.state_dict()
+    ring_b.pri.copy_(ring_a.pri)
+    ring_b.stat.copy_(ring_a.stat)
+    setattr(a.cfg, field, value)
+    a.td3_update(ring_a, 2)
+    b = TD3(cfg(**{field: value}), device=DEV)
+    b.load_state_dict(mid)
+    b.td3_update(ring_b, 2)
+    torch.cuda.synchronize()
+    assert a.per_launches == b.per_launches == (6 if field == "per_alpha" else 0)
+    assert a.nstep_launches == b.nstep_launches == (2 if field == "n_step" else 0)
+    assert _sd_same(a.state_dict(), b.state_dict()) and not _sd_same(mid, b.state_dict())
+    assert torch.equal(ring_a.pri, ring_b.pri) and torch.equal(ring_a.stat, ring_b.stat)
+    assert (field == "per_alpha") == (len(set(ring_a.pri.cpu().tolist())) > 2)

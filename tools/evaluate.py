@@ -61,9 +61,8 @@ def main():
         tr = VecTrainer(n_envs=args.n_envs, hidden=args.hidden, n_hidden=args.n_hidden,
                         batch=args.batch or max(args.n_envs // 2, 1), seed=args.seed,
                         envs_per_group=min(1024, args.n_envs), demos=not args.no_demos,
-                        bc_weight=args.bc_weight, demo_fraction=args.demo_fraction,
-                        per_alpha=args.per_alpha, per_beta=args.per_beta, per_eps=args.per_eps,
-                        n_step=args.n_step, bc_q_filter=args.bc_q_filter)
+                        # the mode fields the command line has (q_weight: the default)
+                        **{k: getattr(args, k) for k in K.MODE_FIELDS if hasattr(args, k)})
     bc = {}
     if args.bc_pretrain > 0:
         bc["bc_loss_before"] = tr.bc_loss(frame=1)
