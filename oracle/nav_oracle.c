@@ -644,7 +644,7 @@ void orc_vec_agent_step_batch(const orc_params_t* p, const float* speed, const f
 enum { TAG_SAMPLE = 4, TAG_TNOISE = 5 };
 
 /* exploration noise of every env at vector step `step`: z [n][2] f64, the Box-Muller pair of
- * philox(0, env, TAG_NOISE, step) (mlp_rows.h k_mlp_fwd: OUT_TICK for nav_act_tick, OUT_ACT for
+ * philox(0, env, TAG_NOISE, step) (rows_kernels.h k_mlp_fwd: OUT_TICK for nav_act_tick, OUT_ACT for
  * nav_act; gauss_pair nav_device.h) = orc_vec_noise_one for env 0 .. n-1 */
 void orc_vec_noise(const orc_params_t* p, int64_t n, uint32_t step, double* z) {
 #ifdef _OPENMP
@@ -654,7 +654,7 @@ void orc_vec_noise(const orc_params_t* p, int64_t n, uint32_t step, double* z) {
 }
 
 /* replay sample indices of one batch: row b reads ring row (philox(b, 0, TAG_SAMPLE, ctr).x *
- * size) >> 32, `size` the ring's fill (sample_row, mlp_rows.h) */
+ * size) >> 32, `size` the ring's fill (sample_row, td3_rows.h) */
 void orc_sample_indices(const orc_params_t* p, int64_t B, int64_t size, uint32_t ctr,
                         int64_t* out) {
 #ifdef _OPENMP
@@ -669,7 +669,7 @@ void orc_sample_indices(const orc_params_t* p, int64_t B, int64_t size, uint32_t
 
 /* target-policy smoothing draws of one batch: eps [B][2] f32 = the Box-Muller pair of
  * philox(row, 0, TAG_TNOISE, ctr) rounded to f32, the value the kernels multiply by policy_noise
- * and clamp (mlp_rows.h k_mlp_fwd OUT_TARGET, td3_critic_rows_body.inc k_td3_critic_rows) */
+ * and clamp (rows_kernels.h k_mlp_fwd OUT_TARGET, td3_critic_rows_body.inc k_td3_critic_rows) */
 void orc_smoothing_noise(const orc_params_t* p, int64_t B, uint32_t ctr, float* eps) {
 #ifdef _OPENMP
 #pragma omp parallel for schedule(static)

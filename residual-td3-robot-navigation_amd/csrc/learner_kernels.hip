@@ -2,7 +2,8 @@
 // gfx950: hidden x hidden weight gradients on MFMA, the fixed-order gradient reduce fused with
 // torch's Adam, multi-net Adam for the shared-policy bucket, Polyak soft updates (all refreshing
 // the packed MFMA weight images), and the replay sampling / copy glue. The row-local half
-// (forward, row backward, the fused train_critic / train_actor row programs) is mlp_rows.h.
+// (forward, row backward, the fused train_critic / train_actor row programs) is rows_kernels.h
+// and td3_rows.h.
 // Here: the plain kernels and their C ABI. The device code they wrap is wgrad.h (weight
 // gradients) and reduce_adam.h (reduce, Adam, Polyak), the argument checks and builders are
 // learner_host.h; the population forms of the same bodies are learner_pop.hip.

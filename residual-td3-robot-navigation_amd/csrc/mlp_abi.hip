@@ -1,6 +1,7 @@
 // mlp_abi.hip — the C ABI (include/navenv.h) of the row kernels: argument checks, the kernels'
-// argument structs (mlp_rows.h) and the dispatch to the launcher object of the network's width
-// and the call's role (mlp_rows_nt.hip, mlp_rows_role.h). No kernel is instantiated here.
+// argument structs (rows_args.h) and the dispatch to the launcher object of the network's width
+// and the call's role (mlp_rows_nt.hip, mlp_rows_role.h). No kernel is instantiated here and no
+// device text is included: the launch contract is all this object shares with the launchers.
 #include "mlp_rows_role.h"
 #include "pop_host.h"
 

@@ -1,5 +1,6 @@
 // mlp_common.h — the device MLP layout (include/navenv.h nav_mlp) and the fragment helpers
-// shared by the row kernels (mlp_rows.h) and the learner kernels (wgrad.h, reduce_adam.h).
+// shared by the row kernels (rows_args.h and the device headers on top of it: rows_gemm.h,
+// rows_layers.h, rows_kernels.h, td3_rows.h) and the learner kernels (wgrad.h, reduce_adam.h).
 #pragma once
 #include <stdlib.h>
 
@@ -8,7 +9,7 @@
 using namespace nav;
 
 // The population learner's table (nav_td3_pop_table_build) is [n_members] row-kernel arguments
-// (mlp_rows.h) followed by [n_members] entries of the cross-row kernels (learner_pop.hip): that
+// (rows_args.h) followed by [n_members] entries of the cross-row kernels (learner_pop.hip): that
 // object's entry size and its check + fill of members' entries into host memory `dst` (NULL:
 // check only), called by the table's entry points.
 int64_t navi_learner_pop_entry_bytes();

@@ -1,8 +1,10 @@
-// mlp_rows_nt.hip — the launchers of the row kernels (mlp_rows.h) of one hidden width, hp = 32 *
+// mlp_rows_nt.hip — the launchers of the row kernels (rows_kernels.h, td3_rows.h; their launch
+// contract is rows_args.h) of one hidden width, hp = 32 *
 // NAV_MLP_PART, and one role (NAV_MLP_ROLE, mlp_rows_role.h): 8 x 7 independent objects, so make
 // -j compiles the heavy template instantiations in parallel. Each exports one dispatcher,
 // nav_mlp_rows_<role>_<NT>(), that mlp_abi.hip calls; the role decides which kernels the object
 // instantiates.
+#include "mlp_rows.h"
 #include "mlp_rows_role.h"
 
 namespace {

@@ -7,9 +7,10 @@
 // compiled beside them, the plain tick kernel came out with a few scalar loads scheduled elsewhere,
 // and the bench's kernels are to stay exactly as the compiler made them (tools/isa_diff.py).
 // The Makefile builds mlp_rows_nt.hip once per (NAV_MLP_ROLE, NAV_MLP_PART); mlp_abi.hip calls
-// the object that rows_role() names.
+// the object that rows_role() names. Both sides need the launch contract (rows_args.h) and no
+// device text: the launchers include that themselves (mlp_rows.h).
 #pragma once
-#include "mlp_rows.h"
+#include "rows_args.h"
 
 // Makefile: ROLES (object name : role)
 enum {

@@ -1,7 +1,7 @@
 // nav_tick.h — the per-env training tick (environment.py:122-137 + robot.py:443-506, 509-538,
 // 645-675, 727-762) as device functions, shared by the standalone tick kernels (env_kernels.hip),
 // the demo-reward passes (demo_reward.hip), the index build (demo_index.hip) and the
-// action-selection kernel that runs the tick in its epilogue (mlp_rows.h).
+// action-selection kernel that runs the tick in its epilogue (rows_kernels.h).
 #pragma once
 #include "nav_device.h"
 

@@ -1,4 +1,4 @@
-// k_td3_actor_rows' statements (mlp_rows.h includes this once per form, as
+// k_td3_actor_rows' statements (td3_rows.h includes this once per form, as
 // td3_critic_rows_body.inc). MODE (constexpr, ACTOR_PLAIN in the plain and population kernels)
 // selects the behaviour-cloning forms of k_td3_actor_rows_bc, whose extras arrive in `bx`:
 // ACTOR_TD3_BC adds the BC term's gradient on rows < bx.B_demo to dL/da, ACTOR_BC_ONLY also runs

@@ -1,4 +1,4 @@
-// k_td3_critic_rows' statements (mlp_rows.h includes this once per form: `a` the arguments,
+// k_td3_critic_rows' statements (td3_rows.h includes this once per form: `a` the arguments,
 // POP and `pv` the population form's flag and launch values, WEIGHTED and `px` the weighted
 // form's flag and extras: k_td3_critic_rows_w)
     extern __shared__ __attribute__((aligned(16))) float smem[];

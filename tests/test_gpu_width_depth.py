@@ -1,6 +1,7 @@
 """The learner and acting kernels at every hidden width and depth against fp64.
 
-mlp_rows_nt.hip (the launchers of the kernels of mlp_rows.h) is compiled once per NT = hidden_pad / 32 (1 .. 8), each object with an
+mlp_rows_nt.hip (the launchers of the kernels of rows_kernels.h and td3_rows.h) is compiled once
+per NT = hidden_pad / 32 (1 .. 8), each object with an
 n_hidden == 1 and an n_hidden >= 2 form and two row-block heights (32-row blocks up to 16 384
 rows, 64-row blocks above); the weight gradients fork on shape (k_wgrad_fact / k_wgrad /
 k_wgrad_gen). Every form is held here to the project's fp64 bars (tests/mlp_ref.py: row quantities
