@@ -42,6 +42,7 @@ extern "C" {
 #define NAV_TAG_TEST 6   /* ctr = (0, env, 6, episode)        test-episode start draw   */
 #define NAV_TAG_DEMO 7   /* ctr = (i, 0, 7, update)           demonstration row index   */
 #define NAV_TAG_PER 8    /* ctr = (b, 0, 8, 2*update [+1])    prioritised sample draw   */
+#define NAV_TAG_DRESET 9 /* ctr = (0, env, 9, episode)  demo-reset coin, demonstration, index */
 
 /* Constants of constants.py / robot.py as a POD (defaults in nav_default_params). */
 typedef struct nav_params {
@@ -716,6 +717,31 @@ int nav_nstep_rows(const nav_replay* replay, const uint8_t* cut, int64_t size, i
                    int64_t stride, int32_t n_step, float gamma, int64_t B, const int64_t* idx,
                    uint32_t seed_lo, uint32_t seed_hi, uint32_t counter, float* staged,
                    int32_t* steps, void* stream);
+/* ---- Resets to demonstration states (Nair et al. 2018, "Overcoming Exploration in RL with
+ * Demonstrations"): some episodes start on a state of a demonstration ----
+ * Runs on the tick's stream after any tick form (nav_agent_step(_indexed), nav_act_tick(_pop)) and
+ * works from what the tick left: env e was reset iff flags[e] & 8 (nav_step_out.flags bit3
+ * 'ended'), env->episodes[e] is already the new episode's number ep and env->state[e] the
+ * init-region draw. For each reset env, with g = e / envs_per_group and
+ * w = philox(0, e, NAV_TAG_DRESET, ep) under the key (seed_lo, seed_hi): if u01(w.x, w.y) < p,
+ * p = prob_group ? prob_group[g] : prob, then d = (w.z * n_demos) >> 32,
+ * t = (w.w * usable[g * n_demos + d]) >> 32 and env->state[e] = (double)demo_states[g * n_demos +
+ * d][t]. demo_states [n_groups * n_demos][T][2] f32, group-major (the CEM's states); usable
+ * [n_groups * n_demos], each in 1 .. T: the leading states of the demonstration an episode may
+ * start on (nav.demos.demo_reset_usable: those outside the goal disc, never the last state).
+ * Nothing else of the SoA is written: hist, meta, plan_index, path_length, episodes and
+ * noise_scale stay as the tick's own reset left them; envs without bit3 are not touched.
+ * prob_group (nullable, device [n_groups], each in [0, 1]) replaces prob per group. counts
+ * (nullable, device [ceil(n/64)], cumulative): counts[e / 64] grows by the number of envs of that
+ * 64-env row that took a demonstration state (each wave owns its slot: deterministic, no
+ * atomics). One env per lane; a lane without bit3 loads its flag byte and nothing else.
+ * NAV_EINVAL (on the host, before any HIP call): env, flags, demo_states or usable NULL, n < 0,
+ * n_demos < 1, T < 2, envs_per_group < 1, prob outside [0, 1] or NaN; then n == 0 returns 0
+ * without a launch; then env->state or env->episodes NULL. */
+int nav_demo_reset(const nav_env_soa* env, const uint8_t* flags, uint32_t seed_lo,
+                   uint32_t seed_hi, const float* demo_states, const int32_t* usable,
+                   int32_t n_demos, int32_t T, int32_t envs_per_group, double prob,
+                   const double* prob_group, int64_t* counts, void* stream);
 /* Fill / strided copy helpers of the TD3 glue (robot.py:329-339, 386-390). */
 int nav_fill(float* x, int64_t n, float value, void* stream);
 int nav_strided_copy(const float* src, int32_t ld_src, int32_t col_src, float* dst, int32_t ld_dst,

@@ -204,6 +204,8 @@ SIGNATURES = [
     ("nav_nstep_rows", C.c_int, [_P(NavReplay), _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                  C.c_float, C.c_int64, _vp, C.c_uint32, C.c_uint32, C.c_uint32,
                                  _vp, _vp, _vp]),
+    ("nav_demo_reset", C.c_int, [_P(NavEnvSoa), _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_int32,
+                                 C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp]),
     ("nav_mlp_mask_count", C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
     ("nav_mlp_row_blocks", C.c_int64, [C.c_int64]),
     ("nav_mlp_edge_count", C.c_int64, [C.c_int32] * 4),

@@ -74,3 +74,19 @@ def demo_set_from(demos, rng=np.random, draws=None):
         for s, _ in augment(states, actions, rng, draws=None if draws is None else draws[k]):
             pts.append(s)
     return np.concatenate(pts, 0) if pts else np.zeros((0, 2))
+
+
+def demo_reset_usable(states, goals, goal_threshold=K.TEST_DISTANCE_THRESHOLD):
+    """The `usable` table of nav_demo_reset: states [J][T][2] (the CEM's demonstrations), goals
+    [J][2] (each demonstration's goal) -> int32 [J]. usable[j] = the number of leading states of
+    demonstration j that lie further than goal_threshold from its goal (f64 distances), clamped
+    to 1 .. T - 1: a reset draws a time index below it, so an episode never starts inside the
+    goal disc and never on the demonstration's last state."""
+    st = np.asarray(states, np.float64)
+    gl = np.asarray(goals, np.float64)
+    J, T = st.shape[0], st.shape[1]
+    assert st.shape == (J, T, 2) and gl.shape == (J, 2) and T >= 2
+    d = st - gl[:, None, :]
+    inside = np.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) <= float(goal_threshold)
+    first = np.where(inside.any(1), inside.argmax(1), T)  # index of the first state inside
+    return np.clip(first, 1, T - 1).astype(np.int32)

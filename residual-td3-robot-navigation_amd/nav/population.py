@@ -32,18 +32,27 @@ transitions of its own env groups' demonstrations; learner="members" runs each T
 epoch loop on its tailed ring, learner="batched" issues one nav_td3_mix_idx_pop per epoch and
 nav_td3_actor_rows_bc_pop in place of nav_td3_actor_rows_pop, from a second device table of the
 members' B_demo, tail sizes and weights. With the keys in no member's overrides nothing changes.
+
+Resets to demonstration states per member: an override demo_reset_prob (not a field of either
+struct) is the probability that an episode of the member's envs starts on a state of one of its
+env group's demonstrations (VecEnv.set_demo_resets; one nav_demo_reset launch after the tick, the
+members' values as its prob_group table, so members must own whole env groups). exploit() hands
+it on like any other field and `explore` may perturb it; the table is rebuilt afterwards. With
+the key in no member's overrides nothing is launched or allocated.
 """
 import ctypes as C
 import dataclasses
 import itertools
 import math
 
+import numpy as np
 import torch
 
 from . import config as K
 from ._lib import (NavMlp, NavParams, NavPopScore, NavReplay, NavTd3Member, NavTd3MemberBc,
                    NavTestOut, lib, params_struct, ptr, stream_handle)
 from .demo_replay import DemoReplay
+from .demos import demo_reset_usable
 from .fields import make_field_device
 from .td3 import TD3
 from .trainer import episode_summary, make_env
@@ -55,8 +64,10 @@ PARAM_KEYS = frozenset(name for name, _ in NavParams._fields_)
 TD3_KEYS = frozenset(f.name for f in dataclasses.fields(K.TD3Config)) - {"batch_size",
                                                                          "num_epochs", "net"}
 # neither struct: the member's starting exploration scale (robot.py:35 INITIAL_NOISE) and the
-# seed of its learner (initial weights, replay sampling, target smoothing)
-EXTRA_KEYS = frozenset({"initial_noise", "seed"})
+# seed of its learner (initial weights, replay sampling, target smoothing); and the env side's
+# demo_reset_prob: the probability that an episode of the member's envs starts on a state of a
+# demonstration (VecEnv.set_demo_resets; it reaches the kernel as prob_group)
+EXTRA_KEYS = frozenset({"initial_noise", "seed", "demo_reset_prob"})
 # population-based training. What a clone keeps of its own: its start values and its learner's
 # seed; every other override it takes from its source
 PBT_OWN_KEYS = frozenset({"initial_noise", "path_length0", "seed"})
@@ -69,7 +80,9 @@ PBT_PARAM_KEYS = frozenset({"demo_factor", "noise_decay", "stuck_penalty", "stuc
 # demonstration prefix of every batch)
 PBT_TD3_KEYS = frozenset({"actor_lr", "critic_lr", "gamma", "tau", "policy_noise", "noise_clip",
                           "max_action", "bc_weight", "q_weight"})
-PBT_EXPLORE_KEYS = PBT_PARAM_KEYS | PBT_TD3_KEYS
+# the env side's per-member floats, fields of neither struct
+PBT_ENV_KEYS = frozenset({"demo_reset_prob"})
+PBT_EXPLORE_KEYS = PBT_PARAM_KEYS | PBT_TD3_KEYS | PBT_ENV_KEYS
 PBT_FACTORS = (0.8, 1.25)
 # learning from the demonstrations, per member (TD3Config)
 BC_KEYS = ("demo_fraction", "bc_weight", "q_weight")
@@ -408,8 +421,9 @@ class PopulationTrainer:
     """VecTrainer for P members at once. `members` is a list of dicts of overrides: fields of
     `nav_params` go to the member's constants (`path_length0` also fills the member's slice of
     path_length after init), fields of TD3Config to its learner, `initial_noise` fills its slice
-    of noise_scale and `seed` seeds its learner. With one member and no overrides every step
-    equals VecTrainer's with the same arguments, bit for bit."""
+    of noise_scale, `seed` seeds its learner and `demo_reset_prob` is the probability that an
+    episode of its envs starts on a demonstration state. With one member and no overrides every
+    step equals VecTrainer's with the same arguments, bit for bit."""
 
     def __init__(self, members, envs_per_member=4096, hidden=256, n_hidden=2, batch=4096,
                  updates_per_step=2, seed=K.RANDOM_SEED, envs_per_group=1024, demos=True,
@@ -430,6 +444,13 @@ class PopulationTrainer:
         if not demos and any(k in ck for _, ck, _ in routed for k in BC_KEYS):
             raise ValueError("demo_fraction / bc_weight / q_weight need demonstrations: "
                              "demos=True")
+        # resets to demonstration states, per member (0 = off for the member)
+        self.demo_reset_probs = [float(ex.get("demo_reset_prob", 0.0)) for _, _, ex in routed]
+        for m, v in enumerate(self.demo_reset_probs):
+            if not 0.0 <= v <= 1.0:
+                raise ValueError(f"demo_reset_prob must lie in [0, 1], got {v} (member {m})")
+        if not demos and any(v > 0 for v in self.demo_reset_probs):
+            raise ValueError("demo_reset_prob needs demonstrations: demos=True")
         # each member's config, and everything it refuses (the modes without a population form,
         # the BC term's Q-filter with the one-launch learner), before anything is built
         cfgs = [K.TD3Config(batch_size=int(batch), num_epochs=int(updates_per_step),
@@ -442,7 +463,8 @@ class PopulationTrainer:
         # demonstrations
         self.bc = any(cfg.bc_on() for cfg in cfgs)
         self.epm = int(envs_per_member)
-        if self.bc:  # members own whole env groups (ValueError otherwise)
+        # members own whole env groups (ValueError otherwise)
+        if self.bc or any(v > 0 for v in self.demo_reset_probs):
             member_demo_groups(0, self.epm, int(envs_per_group) if envs_per_group else self.epm)
         self.n = P * self.epm
         self.device = torch.device(device)
@@ -486,6 +508,8 @@ class PopulationTrainer:
                 self.env.path_length[sl] = int(pk["path_length0"])
         self.pop = PopulationTable([t.actor_network for t in self.td3], self.params, self.rings,
                                    self.epm)
+        self._cem_host = None
+        self._build_demo_resets()
         self.action = torch.zeros(self.n, 2, dtype=torch.float64, device=self.device)
         self.steps = 0
         self.updates_per_step = int(updates_per_step)
@@ -502,6 +526,34 @@ class PopulationTrainer:
 
     def member_slice(self, m):
         return slice(m * self.epm, (m + 1) * self.epm)
+
+    # ---- resets to demonstration states
+    def _build_demo_resets(self):
+        """The env's demo-reset set from the members' present values: each group takes its
+        member's demo_reset_prob (prob_group) and each demonstration's usable count its member's
+        goal_threshold. Nothing while no member has ever had a probability > 0."""
+        if self.env._dreset is None and not any(v > 0 for v in self.demo_reset_probs):
+            return
+        if self._cem is None:
+            raise ValueError("demo_reset_prob needs demonstrations: demos=True")
+        st, _, goals = self._cem
+        if self._cem_host is None:
+            self._cem_host = st.cpu().numpy()
+        usable, prob_group = [], []
+        for m in range(self.P):
+            g, d = member_demo_groups(m, self.epm, self.env.envs_per_group)
+            usable.append(demo_reset_usable(self._cem_host[d.start:d.stop],
+                                            goals[d.start:d.stop], self.params[m].goal_threshold))
+            prob_group += [self.demo_reset_probs[m]] * len(g)
+        self.env.set_demo_resets(st, np.concatenate(usable), 0.0, prob_group)
+
+    def demo_reset_share(self, m):
+        """VecEnv.demo_reset_share over member m's envs (whole 64-env rows). Synchronises."""
+        if self.env.demo_resets is None:
+            return 0.0
+        sl = self.member_slice(m)
+        taken = self.env.demo_resets[sl.start // 64:sl.stop // 64].sum().item()
+        return float(taken) / float(self.env.episodes[sl].sum().item())
 
     # ---- learning from the demonstrations
     def _member_demos(self, m, ring=None):
@@ -643,11 +695,15 @@ class PopulationTrainer:
     def member_value(self, m, key):
         """Member m's present value of a per-member field: the learner's for a TD3Config field,
         else the nav_params field."""
+        if key in PBT_ENV_KEYS:
+            return self.demo_reset_probs[m]
         if key in TD3_KEYS:
             return getattr(self.td3[m].cfg, key)
         return getattr(self.params[m], key)
 
     def _set_member_value(self, m, key, value):
+        if key in PBT_ENV_KEYS:
+            self.demo_reset_probs[m] = float(value)
         if key in PARAM_KEYS:
             setattr(self.params[m], key, value)
         if key in TD3_KEYS:
@@ -679,6 +735,12 @@ class PopulationTrainer:
         if explore and float(explore.get("bc_weight", (0.0, 0.0))[0]) > 0:
             for s in src:
                 dataclasses.replace(self.td3[s].cfg, bc_weight=1.0).check(member=s)
+        # a lower bound above 0 can switch resets on for a population built without them: then
+        # the demonstrations and the whole-groups rule are needed, as at construction
+        if explore and float(explore.get("demo_reset_prob", (0.0, 0.0))[0]) > 0:
+            if self._cem is None:
+                raise ValueError("demo_reset_prob needs demonstrations: demos=True")
+            member_demo_groups(0, self.epm, self.env.envs_per_group)
         if not src:
             return []
         if explore and rng is None:
@@ -689,7 +751,8 @@ class PopulationTrainer:
         lib().nav_td3_pop_exploit(arr, self.P, ptr(tab), (C.c_int32 * n)(*src),
                                   (C.c_int32 * n)(*dst), n, rows, stream_handle(stream))
         # every per-member field but the clone's own: the members' overrides name only some
-        inherited = sorted((PARAM_KEYS | TD3_KEYS) - PBT_OWN_KEYS - {"seed_lo", "seed_hi"})
+        inherited = sorted((PARAM_KEYS | TD3_KEYS | PBT_ENV_KEYS) - PBT_OWN_KEYS
+                           - {"seed_lo", "seed_hi"})
         events = []
         for s, d in zip(src, dst):
             before = {k: self.member_value(d, k) for k in inherited}
@@ -711,6 +774,7 @@ class PopulationTrainer:
                            "explored": {k: values[k] for k in (explore or {})}})
             self.pop.params[d] = self.params[d]
         self.pop.build(stream)
+        self._build_demo_resets()  # the groups' probabilities (prob_group) follow the members
         if self.learner is not None:
             self.learner.rebuild(stream)
         self.pbt_history.extend(events)
@@ -719,7 +783,6 @@ class PopulationTrainer:
     def pbt_rng(self):
         """The generator of pbt_step's draws, seeded once from the trainer's seed."""
         if self._pbt_rng is None:
-            import numpy as np
             self._pbt_rng = np.random.default_rng(self.seed)
         return self._pbt_rng
 

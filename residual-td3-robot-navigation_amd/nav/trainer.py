@@ -19,6 +19,7 @@ from . import prof
 from ._lib import lib, ptr, stream_handle
 from .cem import cem_group_demo_sets
 from .demo_replay import DemoReplay
+from .demos import demo_reset_usable
 from .fields import make_field_device
 from .td3 import TD3
 from .vec_env import ReplayRing, VecEnv, ring_needs
@@ -61,7 +62,7 @@ class VecTrainer:
     def __init__(self, n_envs=65536, hidden=256, n_hidden=2, batch=32768, updates_per_step=2,
                  replay_capacity=None, seed=K.RANDOM_SEED, envs_per_group=1024, demos=True,
                  device="cuda", field=None, grad_hook=None, fuse_tick=True, overlap_collect=False,
-                 demo_rows=None, **modes):
+                 demo_rows=None, demo_reset_prob=0.0, **modes):
         """**modes: the learner's mode fields (config.MODE_FIELDS; any other keyword is a
         TypeError), each at TD3Config's default; what does not combine is TD3Config.check's.
         demo_fraction / bc_weight / q_weight: learning from the demonstrations (TD3Config; off
@@ -76,7 +77,12 @@ class VecTrainer:
         maximum, and batches are drawn in proportion to priority.
         n_step: multi-step returns (TD3Config; off at 1). On, the ring carries one cut mark per
         row, every tick writes its rows' marks from its flags, and the critics' target sums up to
-        n_step rewards along the env's rows (stride n_envs)."""
+        n_step rewards along the env's rows (stride n_envs).
+        demo_reset_prob: resets to demonstration states (Nair et al. 2018; an env-side feature,
+        not a learner mode; off at 0). An episode then starts with this probability on a state of
+        one of its env group's CEM demonstrations instead of the init-region draw (one
+        nav_demo_reset launch after every tick; needs demos=True); env.demo_reset_share()
+        reports the share. evaluate()'s test episodes still start in the init regions."""
         for k in modes:
             if k not in K.MODE_FIELDS:
                 raise TypeError(f"VecTrainer() got an unexpected keyword argument {k!r}")
@@ -88,6 +94,11 @@ class VecTrainer:
         need = ring_needs(cfg)
         if need["tail"] and not demos and demo_rows is None:
             raise ValueError("demo_fraction / bc_weight need demonstrations: demos=True")
+        self.demo_reset_prob = float(demo_reset_prob)
+        if not 0.0 <= self.demo_reset_prob <= 1.0:
+            raise ValueError(f"demo_reset_prob must lie in [0, 1], got {demo_reset_prob}")
+        if self.demo_reset_prob > 0 and not demos:
+            raise ValueError("demo_reset_prob needs demonstrations: demos=True")
         self.n = int(n_envs)
         self.device = torch.device(device)
         self.seed = int(seed)
@@ -96,6 +107,11 @@ class VecTrainer:
         self.field = field
         self.env, self._cem = make_env(self.n, field, self.seed, envs_per_group or self.n, demos,
                                        self.device)
+        if self.demo_reset_prob > 0:  # the CEM's states and, per demonstration, its goal
+            st, _, goals = self._cem
+            self.env.set_demo_resets(st, demo_reset_usable(st.cpu().numpy(), goals,
+                                                           self.env.p.goal_threshold),
+                                     self.demo_reset_prob)
         self.td3 = TD3(cfg, device=self.device, seed=self.seed, grad_hook=grad_hook)
         cap = replay_capacity or max(4 * self.n, 2 * int(batch), K.BUFFER_SIZE)
         # the ring the config needs. The demonstration transitions: in its tail when the learner
@@ -249,6 +265,10 @@ class VecTrainer:
             sd["replay"].update(pri=self.replay.pri.cpu(), stat=self.replay.stat.cpu())
         if self.td3.nstep_on():  # multi-step returns: the cut marks
             sd["replay"].update(cut=self.replay.cut.cpu())
+        if self.demo_reset_prob > 0:  # resets to demonstration states: the set and the counts
+            d = e._dreset
+            sd["demo_reset"] = {"prob": self.demo_reset_prob, "states": d["states"].cpu(),
+                                "usable": d["usable"].cpu(), "counts": e.demo_resets.cpu()}
         return sd
 
     def load_state_dict(self, sd):
@@ -269,6 +289,11 @@ class VecTrainer:
             self.td3.cfg.per_beta = float(m["per_beta"])
         if self.td3.nstep_on():
             self.replay.cut.copy_(sd["replay"]["cut"].to(self.device))
+        dr = sd.get("demo_reset")  # absent in a checkpoint written with the feature off
+        if dr is not None:
+            self.demo_reset_prob = float(dr["prob"])
+            self.env.set_demo_resets(dr["states"], dr["usable"], self.demo_reset_prob)
+            self.env.demo_resets.copy_(dr["counts"].to(self.device))
         self.td3.load_state_dict(sd["td3"])
         self.steps = int(m["steps"])
         self.updates_per_step = int(m["updates_per_step"])

@@ -210,6 +210,11 @@ class VecEnv:
         # launches (A/B and the fused-vs-unfused parity test)
         self.fuse_demo = bool(fuse_demo)
         self._test_out = {}  # (max_steps, traj) -> test_rollout's output tensors
+        # resets to demonstration states (set_demo_resets): the stored set, the taken resets per
+        # 64-env row (int64, cumulative; None until a set is stored) and the launches issued
+        self._dreset = None
+        self.demo_resets = None
+        self.demo_reset_launches = 0
         if init:
             self.init(demo_flag)
 
@@ -269,6 +274,61 @@ class VecEnv:
             return self._shared_off, max(self.n, 1)
         return self.demo_off, self.envs_per_group
 
+    # resets to demonstration states (Nair et al. 2018): after every tick form, an env the tick
+    # reset starts its new episode with probability `prob` on a state of one of its own group's
+    # demonstrations (nav_demo_reset)
+    def set_demo_resets(self, states, usable, prob, prob_group=None):
+        """states [G * n_demos][T][2] float32, group-major (the CEM's demonstrations of the
+        G = ceil(n / envs_per_group) env groups); usable [G * n_demos] int32, each in 1 .. T
+        (nav.demos.demo_reset_usable); prob in [0, 1]; prob_group (optional, [G] values in
+        [0, 1]) replaces prob per group. Stores the set on the device and allocates demo_resets;
+        a later call replaces the set and keeps the counts. While every probability is 0 the
+        ticks launch nothing."""
+        G = (self.n + self.envs_per_group - 1) // self.envs_per_group
+        st = torch.as_tensor(states, dtype=torch.float32).to(self.device).contiguous()
+        us = torch.as_tensor(usable, dtype=torch.int32).to(self.device).contiguous()
+        if st.dim() != 3 or st.shape[2] != 2 or st.shape[1] < 2 or st.shape[0] < G or \
+                st.shape[0] % G != 0 or us.shape != (st.shape[0],):
+            raise ValueError(f"demo resets need states [{G} * n_demos][T >= 2][2] and one usable "
+                             f"count per demonstration; got {tuple(st.shape)}, {tuple(us.shape)}")
+        T = int(st.shape[1])
+        if int(us.min()) < 1 or int(us.max()) > T:
+            raise ValueError(f"usable must lie in 1 .. T = {T}")
+        prob = float(prob)
+        if not 0.0 <= prob <= 1.0:
+            raise ValueError(f"demo reset probability must lie in [0, 1], got {prob}")
+        pg = None
+        if prob_group is not None:
+            pg = torch.as_tensor(prob_group, dtype=torch.float64).reshape(-1)
+            if pg.shape[0] != G or not bool(((pg >= 0) & (pg <= 1)).all()):
+                raise ValueError(f"prob_group must be {G} values in [0, 1]")
+        on = prob > 0 if pg is None else bool((pg > 0).any())
+        self._dreset = {"states": st, "usable": us, "n_demos": int(st.shape[0]) // G, "T": T,
+                        "prob": prob, "prob_group": None if pg is None else pg.to(self.device),
+                        "on": on}
+        if self.demo_resets is None:
+            self.demo_resets = torch.zeros((self.n + 63) // 64, dtype=torch.int64,
+                                           device=self.device)
+
+    def _demo_reset(self, stream=None):
+        """nav_demo_reset on the tick's stream, iff a set is stored and some probability is > 0."""
+        d = self._dreset
+        if d is None or not d["on"]:
+            return
+        self.demo_reset_launches += 1
+        lib().nav_demo_reset(C.byref(self.soa), ptr(self.flags), self.p.seed_lo, self.p.seed_hi,
+                             ptr(d["states"]), ptr(d["usable"]), d["n_demos"], d["T"],
+                             self.envs_per_group, d["prob"], ptr(d["prob_group"]),
+                             ptr(self.demo_resets), stream_handle(stream))
+
+    def demo_reset_share(self):
+        """demo_resets.sum() / episodes.sum(): the episodes started on a demonstration state over
+        the envs' episode numbers (which count from the reference's demonstration-phase episodes,
+        nav_env_init). 0.0 without a stored set. Synchronises."""
+        if self.demo_resets is None:
+            return 0.0
+        return float(self.demo_resets.sum().item()) / float(self.episodes.sum().item())
+
     # one fused training tick (robot.py:443-506, 645-675 + environment.py:122-137)
     def agent_step(self, action, replay, stream=None, reward_out=None):
         base = replay.position
@@ -285,6 +345,7 @@ class VecEnv:
                     ptr(ix.cell_start), ptr(ix.cand), ptr(reward_out), s)
             replay.advance(self.n)
             replay.stamp(base, self.n, stream, self.flags)
+            self._demo_reset(stream)
             return base
         has_demo = self.demo_xy is not None and self.demo_xy.shape[0] > 0
         with prof.region("agent_step", float(prof.AGENT_STEP_BYTES * self.n)):
@@ -295,6 +356,7 @@ class VecEnv:
             self.demo_reward(replay, base, reward_out=reward_out, stream=stream)
         replay.advance(self.n)
         replay.stamp(base, self.n, stream, self.flags)
+        self._demo_reset(stream)
         return base
 
     # the two-launch tick's second launch: the demo-proximity term (robot.py:749-757) of the envs
@@ -343,6 +405,7 @@ class VecEnv:
                 ptr(action_out), ptr(reward_out), stream_handle(stream))
         replay.advance(self.n)
         replay.stamp(base, self.n, stream, self.flags)
+        self._demo_reset(stream)
         return base
 
     # robot-learning.py:78, 104-117 for every env: one greedy test episode per env in ONE launch
@@ -402,6 +465,7 @@ class VecEnv:
                 self.envs_per_group, ptr(ix.cell_start) if ix else None,
                 ptr(ix.cand) if ix else None, ptr(action_out), ptr(reward_out),
                 stream_handle(stream))
+        self._demo_reset(stream)
 
     # test_rollout with member m's actor, max_action and goal_threshold on its envs
     # (nav_test_rollout_pop); the same output tensors as test_rollout

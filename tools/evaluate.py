@@ -11,7 +11,10 @@ before and after to the line; --bc-weight / --demo-fraction train with the demon
 (--bc-q-filter: a demonstration row is cloned only where critic 1 rates its action above the
 policy's; the line gains bc_kept_fraction, the share the last policy epoch kept);
 --per-alpha / --per-beta / --per-eps train with prioritised replay (not together with those two);
---n-step N trains on N-step returns (with prioritised replay or alone, not with those two).
+--n-step N trains on N-step returns (with prioritised replay or alone, not with those two);
+--demo-reset-prob P starts a training episode with probability P on a state of one of its env
+group's demonstrations (with any of the above; the line gains demo_reset_prob and
+demo_reset_share, the episodes started that way over the envs' episode numbers).
 """
 import argparse
 import json
@@ -50,6 +53,8 @@ def main():
                     help="prioritised replay: added to |TD error| before the exponent")
     ap.add_argument("--n-step", type=int, default=1,
                     help="multi-step returns: the longest horizon (1 = off, at most 16)")
+    ap.add_argument("--demo-reset-prob", type=float, default=0.0,
+                    help="resets to demonstration states: the probability per episode (0 = off)")
     args = ap.parse_args()
     import torch
     from nav._lib import require_gpu
@@ -61,6 +66,7 @@ def main():
         tr = VecTrainer(n_envs=args.n_envs, hidden=args.hidden, n_hidden=args.n_hidden,
                         batch=args.batch or max(args.n_envs // 2, 1), seed=args.seed,
                         envs_per_group=min(1024, args.n_envs), demos=not args.no_demos,
+                        demo_reset_prob=args.demo_reset_prob,
                         # the mode fields the command line has (q_weight: the default)
                         **{k: getattr(args, k) for k in K.MODE_FIELDS if hasattr(args, k)})
     bc = {}
@@ -78,6 +84,9 @@ def main():
         res["n_step"] = tr.td3.cfg.n_step
     if tr.td3.cfg.bc_q_filter:
         res["bc_kept_fraction"] = tr.td3.bc_kept_fraction()
+    if tr.demo_reset_prob > 0:
+        res["demo_reset_prob"] = tr.demo_reset_prob
+        res["demo_reset_share"] = tr.env.demo_reset_share()
     res.update(bc)
     # strict JSON: a NaN (no env reached) prints as null
     print(json.dumps({k: None if isinstance(v, float) and v != v else v for k, v in res.items()}))

@@ -10,6 +10,8 @@ numbers of evaluate().
     python tools/sweep.py --axis initial_noise=1,0.5 --axis noise_decay=0.5,0.75,0.9 --replicas 3
     python tools/sweep.py --reference-study --replicas 2 --pbt-every 50 \\
         --pbt-explore demo_factor=1:100 --pbt-explore critic_lr=1e-5:1e-2
+    python tools/sweep.py --axis demo_reset_prob=0,0.25,0.5 --pbt-every 50 \\
+        --pbt-explore demo_reset_prob=0:1
 
 --reference-study runs the four DEMO_PROXIMITY_FACTOR values of the reference's published figure
 (average_score_by_demonstration_proximity.png); the second form is simulator.py:169-200's
@@ -135,6 +137,9 @@ def main(argv=None):
     for m, row in enumerate(tr.evaluate(max_steps=a.test_steps)):
         if tr.bc:  # learning from the demonstrations: every member's three values, set or default
             row.update({k: tr.member_value(m, k) for k in BC_KEYS})
+        if tr.env.demo_resets is not None:  # resets to demonstration states: value and share
+            row.update(demo_reset_prob=tr.member_value(m, "demo_reset_prob"),
+                       demo_reset_share=tr.demo_reset_share(m))
         print(json.dumps({"member": m, "replica": replica[m], "train_steps": a.train_steps,
                           **row}), flush=True)
 
