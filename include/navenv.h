@@ -11,7 +11,16 @@
  *    no allocation, no synchronisation inside a launch function (graph-capturable);
  *  - return 0 on success, NAV_EINVAL for a bad argument (checked on the host before any launch),
  *    or -(hipError_t) when a launch fails; nothing aborts;
- *  - one caller thread per stream; the library keeps no global mutable state.
+ *  - one caller thread per stream; the library keeps no global mutable state;
+ *  - outputs and workspaces (learner and acting entry points: the MLP, TD3, glue and tick launches):
+ *    a launch writes every element of the extent documented for an output, reads none of them
+ *    before it has written it, and stores nowhere else, so no buffer has to be zeroed or otherwise
+ *    prepared by the caller. The elements a launch leaves as they were are named at its entry
+ *    point: layers whose save-mask bit is clear, columns outside [out_col, out_col + d_out), the
+ *    part of an edge slab another launch produces, mask-image row tiles past the last row
+ *    workgroup (nav_mlp_mask_count), q_demo rows >= B_demo, ring / cut / pri entries outside the
+ *    written window, and any output passed as NULL. Inputs (networks that are only read, the ring,
+ *    idx, eps, w, cut) are never written. tests/test_gpu_footprint.py holds every launch to this.
  *
  * Reference interface each entry replaces is cited as file:line of /root/reference.
  */
@@ -405,8 +414,11 @@ int nav_pop_test_summary(const nav_test_out* out, int32_t n_members, int32_t env
  * out_mode 1 (target policy smoothing, robot.py:336-339): out = clamp(y + clamp(policy_noise*eps,
  * +-noise_clip), +-max_action) with eps from `eps` [M][2] f32 if given else Philox
  * (NAV_TAG_TNOISE, counter). acts (nullable, per net): [n_hidden][M][hp] post-ReLU activations,
- * layer L written when bit L of save_mask is set; masks (nullable, per net): nav_mlp_mask_count
- * u16 words of ReLU-derivative bits (for nav_mlp_backward / nav_mlp_wgrad). */
+ * layer L written when bit L of save_mask is set (rows [0, M) of that layer in full, the padded
+ * columns as exact zeros; the other layers are not touched); masks (nullable, per net):
+ * nav_mlp_mask_count u16 words of ReLU-derivative bits (for nav_mlp_backward / nav_mlp_wgrad),
+ * written as that function's comment states. out: columns [out_col, out_col + d_out) of rows
+ * [0, M) are written, the other columns of an ld_out > d_out row are not touched. */
 int nav_mlp_forward(const nav_mlp* nets, int32_t n_nets, int64_t M, const float* in,
                     int32_t ld_in, int32_t in_col, float* const* out, int32_t ld_out,
                     int32_t out_col, int32_t out_mode, const float* eps, float policy_noise,
@@ -422,7 +434,8 @@ int nav_mlp_forward(const nav_mlp* nets, int32_t n_nets, int64_t M, const float*
  * edge_slabs, acts/save_mask, masks). With row_backward != 0 each online critic's row backward
  * (robot.py:361) follows its forward in the same launch, as nav_mlp_backward of dq with the
  * batch's (s, a) columns as input: W0 / bias partials into edge_slabs, dz rows of dz_save_mask
- * layers into dz[i] — the caller then skips nav_mlp_backward. split_twins: 1 = the twin online
+ * layers into dz[i] (layers without their bit, and all of dz with row_backward == 0, are not
+ * touched) — the caller then skips nav_mlp_backward. split_twins: 1 = the twin online
  * critics in separate workgroups (grid.y = 2, each repeating the target passes: the small-batch
  * form), 0 = both in one workgroup, < 0 = the library's choice (split for B <= 2048); the
  * results are bit-identical either way. */
@@ -506,14 +519,30 @@ int nav_td3_actor_rows_bcq(const nav_mlp* actor, const nav_mlp* critic, const na
                            float* q_demo, int32_t* keep_part, float* acts, uint32_t save_mask,
                            float* dz, uint32_t dz_save_mask, uint16_t* masks_actor,
                            uint16_t* masks_critic, float* edge_slabs, void* stream);
-/* u16 words of the ReLU mask image for M rows (layout: [n_hidden][row tiles][hp/32][64]). */
+/* u16 words of the ReLU mask image for M rows (layout: [n_hidden][row tiles][hp/32][64], row tile
+ * = row / 32, layers strided by T = 4 * ceil(M / 128) row tiles). Every launch that writes masks
+ * (nav_mlp_forward, nav_td3_critic_forward, nav_td3_critic_rows(_w), nav_td3_actor_rows(_bc,
+ * _bcq) and their population forms) writes, per layer, all [hp/32][64] words of row tiles
+ * [0, R * nav_mlp_row_blocks(M)), R = 1 up to 16384 rows and 2 above (a row workgroup's height
+ * / 32): that covers every row < M, the rows past M inside a written tile carry the bits of an
+ * all-zero input row, and the empty second tile of a last 64-row workgroup is written too. Row
+ * tiles from R * nav_mlp_row_blocks(M) up to T are never written and never read. */
 int64_t nav_mlp_mask_count(int32_t hidden_pad, int32_t n_hidden, int64_t M);
 /* Parameter gradients are produced in two parts that nav_grad_reduce combines:
  *  - edge slabs [row blocks][nav_mlp_edge_count]: per row block of the forward/backward launches
  *    (nav_mlp_row_blocks(M) blocks), partial sums of every parameter except the hidden x hidden
- *    weights, in the flat order with those segments cut out (W0 | b0 .. b_{n_hidden-1} | Wo | bo);
+ *    weights, in the flat order with those segments cut out (W0 | b0 .. b_{n_hidden-1} | Wo | bo).
+ *    A slab is produced in two parts, each written in full for every block, the last, partial
+ *    block included: the output layer's part (Wo | bo and the rounding slots behind bo, as zeros)
+ *    and the rest (W0 and every hidden bias, padded units as zeros). nav_td3_critic_forward and
+ *    nav_td3_critic_rows(_w) with row_backward == 0 write the output layer's part alone;
+ *    nav_mlp_backward writes the rest, and the output layer's part too when h_top is given;
+ *    nav_td3_critic_rows(_w) with row_backward != 0 and nav_td3_actor_rows(_bc, _bcq) write both.
+ *    nav_grad_reduce* reads every entry of every block, so both parts must have been produced;
  *  - hidden slabs [splits][nav_mlp_hidden_count]: nav_mlp_wgrad's split-M partials of
- *    W_1 .. W_{n_hidden-1}. */
+ *    W_1 .. W_{n_hidden-1}; every entry of every split is written, a split whose rows
+ *    [s*P, (s+1)*P) of nav_mlp_wgrad's comment all lie at or past M as zeros (of either sign).
+ * Per-block outputs (loss_part, bc_part, keep_part) get one value per row block, every block. */
 int64_t nav_mlp_row_blocks(int64_t M);
 int64_t nav_mlp_edge_count(int32_t d_in, int32_t d_out, int32_t hidden_pad, int32_t n_hidden);
 int64_t nav_mlp_hidden_count(int32_t hidden_pad, int32_t n_hidden);
@@ -530,8 +559,9 @@ int nav_td3_critic_forward(const nav_mlp* nets, int64_t B, const float* in, int3
 /* Row-local backward (autograd of robot.py:355-395) of 1 or 2 networks of the same shape that
  * share the input rows (the twin critics: one launch): per net i, dL/dy rows
  * dy[i][m*ld_dy + 0..d_out) (ld_dy 0: one row for all) and the forward's ReLU masks[i] give dL/dz
- * of every hidden layer, dz_L written to dz[i] [n_hidden][M][hp] for bits L of save_mask;
- * dx[i] (nullable) [M][d_in] = dL/dx. edge_slabs[i] (nullable): per-block W0 / bias partials
+ * of every hidden layer, dz_L written to dz[i] [n_hidden][M][hp] for bits L of save_mask (the
+ * other layers are not touched); dx[i] (nullable) [M][d_in] = dL/dx.
+ * edge_slabs[i] (nullable): per-block W0 / bias partials
  * (input rows from `in`), plus Wo / bo when h_top[i] [M][hp] (top hidden activations) is given.
  * Pointer arrays themselves may be NULL where every entry would be. */
 int nav_mlp_backward(const nav_mlp* nets, int32_t n_nets, int64_t M, const float* const* dy,
@@ -541,7 +571,7 @@ int nav_mlp_backward(const nav_mlp* nets, int32_t n_nets, int64_t M, const float
                      void* stream);
 /* Hidden x hidden weight gradients dW_L = dz_L^T h_{L-1} of 1 or 2 networks (one launch) as
  * `splits` partial slabs slabs[i] [splits][nav_mlp_hidden_count] (rows of split s =
- * [s*P, (s+1)*P), P = ceil(M/splits) rounded up to 64). h_0 is recomputed from `in`,
+ * [s*P, (s+1)*P), P = ceil(M/splits) rounded up to 32). h_0 is recomputed from `in`,
  * dz_{n_hidden-1} from dy[i] and masks[i]; acts[i] / dz[i] (saved layers 1 .. n_hidden-2) are
  * read only for n_hidden > 2. Any splits >= 1 is valid; nav_mlp_wgrad_splits gives the count
  * that fills the chip (one tile workgroup per CU; for d_out = 1 at n_hidden = 2 the tile is
@@ -554,7 +584,11 @@ int nav_mlp_wgrad(const nav_mlp* nets, int32_t n_nets, int64_t M, const float* i
                   const uint16_t* const* masks, float* const* slabs, int32_t splits,
                   void* stream);
 /* grad [param_count] = sum of the hidden slabs (hidden weights) and of the edge slabs (the rest),
- * in a fixed order. */
+ * in a fixed order: all nav_mlp_param_count entries are written, the padded and rounding slots
+ * as the sums of the slabs' zeros. The Adam and soft-update forms below write all
+ * nav_mlp_param_count entries of params, m, v (and grads, targets) and all nav_mlp_packed_count
+ * entries of every packed image they refresh; a padded slot of params, m and v whose gradient
+ * slot is zero stays exactly +0.0f. */
 int nav_grad_reduce(const nav_mlp* net, const float* hidden_slabs, int32_t splits,
                     const float* edge_slabs, int64_t edge_blocks, float* grad, void* stream);
 /* nav_grad_reduce fused with the Adam step (robot.py:236-239, as nav_adam) of 1 or 2 networks in
