@@ -5,6 +5,8 @@ and robot.py:21-54 (demo augmentation, path length, exploration, replay, reward 
 """
 from dataclasses import dataclass, field
 
+from ._abi import parse_header
+
 # constants.py
 WORLD_SIZE = 100
 ROBOT_MAX_ACTION = 5
@@ -51,7 +53,7 @@ GAMMA = 0.99
 TAU = 0.001
 
 # include/navenv.h
-NSTEP_MAX = 16  # NAV_NSTEP_MAX: the longest multi-step return
+NSTEP_MAX = parse_header()[0]["NAV_NSTEP_MAX"]  # the longest multi-step return
 
 
 @dataclass

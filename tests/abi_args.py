@@ -19,10 +19,17 @@ def load_raw():
     return _lib.lib().raw
 
 
+SPELLED = {"in": "inp"}  # a header parameter name that Python keeps for itself
+
+
 class Call:
-    """A valid argument set of one entry point, by name; a case alters some of them."""
+    """A valid argument set of one entry point, by name; a case alters some of them. The names
+    are include/navenv.h's parameter names in its order: the arguments are passed by position."""
 
     def __init__(self, fn, **valid):
+        from nav._abi import parse_header
+        declared = [SPELLED.get(name, name) for _, name in parse_header()[2][fn][1]]
+        assert list(valid) == declared, (fn, list(valid), declared)
         self.fn, self.valid = fn, valid
 
     def __call__(self, lib, **changed):

@@ -50,7 +50,8 @@ _IDX = dict(demo_xy=v(F), demo_off=v(F), envs_per_group=v(13), cell_start=v(F), 
 _GROUPS = dict(demo_xy=v(F), demo_off=v(F), n_groups=v(2))
 
 CALLS = {c.fn: c for c in (
-    Call("nav_env_init", **_P, env=env(), epg=v(13), demo_flag=v(0), draws_out=v(None), **_S),
+    Call("nav_env_init", **_P, env=env(), envs_per_group=v(13), demo_flag=v(0),
+         draws_out=v(None), **_S),
     Call("nav_env_reset", **_P, env=env(), mask=v(None), uniforms=v(None), **_S),
     Call("nav_env_step", **_P, env=env(), field=v(F), action=v(F), next_state=v(None), **_S),
     Call("nav_env_step_k", **_P, env=env(), field=v(F), actions=v(F), K=v(3), next_states=v(None),
@@ -68,7 +69,7 @@ CALLS = {c.fn: c for c in (
     Call("nav_replay_push", replay=replay(), base=v(3), n=v(65), state=v(F), action=v(F),
          reward=v(F), next_state=v(F), done=v(F), **_S),
     Call("nav_demo_reward", **_P, n=v(65), next_state=v(F), goal_term=v(F), flags=v(F),
-         demo_xy=v(F), demo_off=v(F), m=v(0), epg=v(13), **_RING, reward_out=v(None),
+         demo_xy=v(F), demo_off=v(F), m=v(0), envs_per_group=v(13), **_RING, reward_out=v(None),
          block_stats=v(None), **_S),
     Call("nav_demo_reward_indexed", **_P, n=v(65), next_state=v(F), goal_term=v(F), flags=v(F),
          **_IDX, **_RING, reward_out=v(None), block_stats=v(None), **_S),
@@ -134,8 +135,8 @@ BAD = (
     nulls("nav_env_init", "p", "env") + env_nulls("nav_env_init", *ENV_PTRS) + [
         ("nav_env_init", "n < 0", dict(env=env(-1))),
         ("nav_env_init", "n = 2^31", dict(env=env(1 << 31))),
-        ("nav_env_init", "epg = 0", dict(epg=v(0))),
-        ("nav_env_init", "epg = 0 and no envs", dict(epg=v(0), env=EMPTY_ENV)),
+        ("nav_env_init", "epg = 0", dict(envs_per_group=v(0))),
+        ("nav_env_init", "epg = 0 and no envs", dict(envs_per_group=v(0), env=EMPTY_ENV)),
         ("nav_env_init", "max_goal_draws = 0", dict(p=params(max_goal_draws=0))),
     ] + nulls("nav_env_reset", "p", "env") + env_nulls("nav_env_reset", "state", "region") + [
         ("nav_env_reset", "n < 0", dict(env=env(-1))),
@@ -180,8 +181,8 @@ BAD = (
     ] + nulls("nav_demo_reward", "p", "next_state", "goal_term", "flags")
     + ring("nav_demo_reward", False) + [
         ("nav_demo_reward", "n < 0", dict(n=v(-1))),
-        ("nav_demo_reward", "demo_off and epg = 0", dict(epg=v(0))),
-        ("nav_demo_reward", "demo_off and epg = 0 and n = 0", dict(epg=v(0), n=v(0))),
+        ("nav_demo_reward", "demo_off and epg = 0", dict(envs_per_group=v(0))),
+        ("nav_demo_reward", "demo_off and epg = 0 and n = 0", dict(envs_per_group=v(0), n=v(0))),
         ("nav_demo_reward", "shared demos, m > 0, no demo_xy",
          dict(demo_off=v(None), m=v(7), demo_xy=v(None))),
     ] + nulls("nav_demo_reward_indexed", "p", "next_state", "goal_term", "flags", "demo_xy",
