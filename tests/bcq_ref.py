@@ -86,7 +86,7 @@ def bcq_case(hidden, nh, B, b_demo, seed=None):
         p = make_mlp_params(100 * seed + k, [d_in] + [hidden] * nh + [d_out])
         layers[name] = [(torch.tensor(W), torch.tensor(b)) for W, b in p]
     return dict(rows=rows.contiguous(), idx_a=idx, layers=layers, B=B, b_demo=b_demo,
-                hidden=hidden, nh=nh)
+                hidden=hidden, nh=nh, ring=N_ROWS)
 
 
 def filter_shares(ref):

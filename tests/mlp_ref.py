@@ -331,7 +331,7 @@ def epoch_case(hidden, nh, B, K=None):
             ks = ks_actor if name in ("ta", "actor", "atgt") else ks_critic
             layers[name], _ = shift_layers(layers[name], 0, ks)
     return dict(rows=rows, idx=idx, idx_a=idx_a, eps=eps, layers=layers, B=B, hidden=hidden,
-                nh=nh)
+                nh=nh, ring=RING)
 
 
 def critic_quantities(e, k):

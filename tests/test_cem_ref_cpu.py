@@ -7,6 +7,7 @@ import pytest
 
 import cem_ref
 from conftest import golden
+from gpu_support import ulps_f32
 
 TRACES = ["trace.npz", "trace_branches.npz", "trace_branches_field.npz"]
 P, T, I, E = 100, 200, 4, 10   # environment.py's CEM constants
@@ -15,12 +16,6 @@ P, T, I, E = 100, 200, 4, 10   # environment.py's CEM constants
 @pytest.fixture(scope="module", autouse=True)
 def _oracle_built(orc):
     return orc
-
-
-def ulps_f32(a, b):
-    a = np.asarray(a, np.float32).view(np.int32).astype(np.int64)
-    b = np.asarray(b, np.float32).view(np.int32).astype(np.int64)
-    return np.abs(a - b)
 
 
 def consume_init_and_goal(rs):

@@ -14,22 +14,18 @@ import pytest
 import torch
 
 import bc_ref as BR
+import launches as LN
 import mlp_ref as R
-from test_gpu_width_depth import _device_net, _equal_nan, _ids, _nan
+from gpu_support import equal_nan as _equal_nan, ids as _ids, nav  # noqa: F401
+from launches import nan as _nan
+from pop_support import same as _same, snapshot
+from trace_support import assert_demo_rows, demo_cases
 
 pytestmark = pytest.mark.gpu
 DEV = R.DEV
-SEED = 1707366464
+SEED = LN.SEED
+NAN = float("nan")
 BIG = 16421  # 64-row blocks, the last one partial
-
-
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    import nav as navpkg
-    return navpkg
 
 
 # ---- nav_demo_transitions ----
@@ -77,7 +73,6 @@ def test_demo_transitions_vs_reference_pushes(nav, case):
     columns equal, the reward equal or one float32 ulp from float32(push_r), rows inside
     the goal radius exactly 50."""
     from nav._lib import lib, params_struct, ptr, stream_handle
-    from test_oracle_branches_cpu import assert_demo_rows, demo_cases
     name, st, ac, goals, want, rew = demo_cases()[case]
     n, T = st.shape[:2]
     rows = _nan(n * (T - 1), 8)
@@ -107,30 +102,13 @@ def _mix(b_demo, both=True):
     return ic, ia
 
 
-def _rows_batches(nets, rd, idx_c, idx_a, eps):
+def _rows_batches(nets, dev, idx_c, idx_a):
     """The `batch` outputs of the existing nav_td3_critic_rows / nav_td3_actor_rows launches at
-    MIX's counter with the given indices (None: the kernels' own Philox draw)."""
-    from nav._lib import descs, lib, parr, ptr, stream_handle
-    L, s, B = lib(), stream_handle(), MIX["B"]
-    cr = [nets["cr0"], nets["cr1"]]
-    hp, nh = cr[0].hp, cr[0].n_hidden
-    nblk = L.nav_mlp_row_blocks(B)
-    ec = L.nav_mlp_edge_count(4, 1, hp, nh)
-    bc, ba = _nan(B, 8), _nan(B, 8)
-    dq, lp = [_nan(B), _nan(B)], _nan(2, nblk)
-    es = [_nan(nblk, ec), _nan(nblk, ec)]
-    masks = [c.mask_buffer(B) for c in cr]
-    assert L.nav_td3_critic_rows(
-        C.byref(nets["ta"].desc()), descs(nets["tc0"], nets["tc1"]), descs(*cr), C.byref(rd),
-        MIX["size"], B, ptr(idx_c), SEED & 0xFFFFFFFF, SEED >> 32, MIX["counter"], ptr(eps), 0.2,
-        0.5, 5.0, 0.99, ptr(bc), parr(*dq), parr(lp[0], lp[1]), parr(*es), None, 0, parr(*masks),
-        1, None, 0, -1, s) == 0
-    a = nets["actor"]
-    assert L.nav_td3_actor_rows(
-        C.byref(a.desc()), C.byref(cr[0].desc()), C.byref(rd), MIX["size"], B, ptr(idx_a),
-        SEED & 0xFFFFFFFF, SEED >> 32, MIX["counter"], ptr(ba), None, ptr(_nan(B, 2)), None, 0,
-        None, 0, ptr(a.mask_buffer(B)), ptr(masks[0]),
-        ptr(_nan(nblk, L.nav_mlp_edge_count(2, 2, hp, nh))), s) == 0
+    MIX's counter with the given indices (None: the kernels' own Philox draw), nothing saved."""
+    dev = dict(dev, idx=idx_c, idx_a=idx_a, size=MIX["size"])
+    kw = dict(fill=NAN, save=False, counter=MIX["counter"])
+    bc = LN.critic_rows(nets, dev, MIX["B"], **kw)["batch"]
+    ba = LN.actor_rows(nets, dev, MIX["B"], form="plain", **kw)["batch"]
     torch.cuda.synchronize()
     return bc, ba
 
@@ -138,20 +116,12 @@ def _rows_batches(nets, rd, idx_c, idx_a, eps):
 def test_mix_idx_without_demonstrations_is_the_kernels_own_draw(nav):
     """B_demo = 0: idx_critic / idx_actor fed to the existing row kernels give the batch the
     same launches draw themselves with idx = NULL at the same counter, bit for bit."""
-    from nav._lib import NavReplay
-    case = R.epoch_case(64, 2, MIX["B"])
-    nets = {}
-    for name, layers in case["layers"].items():
-        d_in, d_out = (2, 2) if name in ("ta", "actor", "atgt") else (4, 1)
-        nets[name] = _device_net(layers, d_in, d_out, 64, 2)
-    rows = case["rows"].to(DEV).contiguous()
-    rows[:, 0] = torch.arange(R.RING, device=DEV)  # every row distinct
-    rd = NavReplay(rows.data_ptr(), R.RING)
-    eps = case["eps"].to(DEV).contiguous()
+    nets, dev = LN.device_epoch(R.epoch_case(64, 2, MIX["B"]))
+    dev["rows"][:, 0] = torch.arange(R.RING, device=DEV)  # every row distinct
     ic, ia = _mix(0)
     assert int(ic.min()) >= 0 and int(ic.max()) < MIX["size"] and not torch.equal(ic, ia)
-    got = _rows_batches(nets, rd, ic, ia, eps)
-    want = _rows_batches(nets, rd, None, None, eps)
+    got = _rows_batches(nets, dev, ic, ia)
+    want = _rows_batches(nets, dev, None, None)
     for g, w, idx in zip(got, want, (ic, ia)):
         assert torch.equal(g, w)
         assert torch.equal(g[:, 0].long(), idx)
@@ -177,46 +147,19 @@ def test_mix_idx_demonstration_rows_vs_host_philox(nav, orc, b_demo):
 
 # ---- the BC forms of the actor row kernel ----
 def _bc_setup(hidden, nh, B, b_demo):
-    from nav._lib import NavReplay
     case = BR.bc_case(hidden, nh, B, b_demo)
-    nets = {n: _device_net(case["layers"][n], *((2, 2) if n == "actor" else (4, 1)), hidden, nh)
-            for n in ("actor", "cr0")}
-    dev = dict(rows=case["rows"].to(DEV).contiguous(), idx_a=case["idx_a"].to(DEV))
-    dev["rd"] = NavReplay(dev["rows"].data_ptr(), R.RING)
-    return case, nets, dev
+    return (case, *LN.device_epoch(case))
 
 
 def _actor_rows_bc(nets, dev, B, b_demo, q_weight, bc_weight, critic=True, plain=False):
-    """nav_td3_actor_rows_bc (plain: nav_td3_actor_rows) into NaN-prefilled buffers, as
-    test_gpu_width_depth._actor_rows launches the plain form; then the weight gradients and the
-    reduce into the actor's flat gradient `g`."""
-    from nav._lib import descs, lib, parr, ptr, stream_handle
-    L, s = lib(), stream_handle()
-    actor, cr = nets["actor"], nets["cr0"]
-    hp, nh = actor.hp, actor.n_hidden
-    mid = actor.middle_layers()
-    nblk = L.nav_mlp_row_blocks(B)
-    o = dict(batch=_nan(B, 8), q=_nan(B), da=_nan(B, 2), acts=_nan(nh, B, hp), dz=_nan(nh, B, hp),
-             ma=actor.mask_buffer(B), mc=cr.mask_buffer(B), part=_nan(nblk),
-             es=_nan(nblk, L.nav_mlp_edge_count(2, 2, hp, nh)), nblk=nblk)
-    head = (C.byref(actor.desc()), C.byref(cr.desc()) if critic else None, C.byref(dev["rd"]),
-            R.RING, B, ptr(dev["idx_a"]), SEED & 0xFFFFFFFF, SEED >> 32, 3)
-    tail = (ptr(o["acts"]), mid, ptr(o["dz"]), mid, ptr(o["ma"]), ptr(o["mc"]) if critic else None,
-            ptr(o["es"]), s)
-    qp = ptr(o["q"]) if critic else None
+    """nav_td3_actor_rows_bc (plain: nav_td3_actor_rows) into NaN-prefilled buffers; then the
+    weight gradients and the reduce into the actor's flat gradient `g`."""
     if plain:
-        assert L.nav_td3_actor_rows(*head, ptr(o["batch"]), qp, ptr(o["da"]), *tail) == 0
+        o = LN.actor_rows(nets, dev, B, form="plain", fill=NAN)
     else:
-        assert L.nav_td3_actor_rows_bc(*head, b_demo, q_weight, bc_weight, ptr(o["batch"]), qp,
-                                       ptr(o["da"]), ptr(o["part"]), *tail) == 0
-    splits = int(L.nav_mlp_wgrad_splits(1, 2, hp, nh, B))
-    hs = _nan(splits, max(4, L.nav_mlp_hidden_count(hp, nh)))
-    assert L.nav_mlp_wgrad(descs(actor), 1, B, ptr(o["batch"]), 8, 0, parr(o["acts"]),
-                           parr(o["dz"]), parr(o["da"]), 2, parr(o["ma"]), parr(hs), splits,
-                           s) == 0
-    o["g"] = _nan(actor.count)
-    assert L.nav_grad_reduce(C.byref(actor.desc()), ptr(hs), splits, ptr(o["es"]), nblk,
-                             ptr(o["g"]), s) == 0
+        o = LN.actor_rows(nets, dev, B, form="bc", fill=NAN, b_demo=b_demo, q_weight=q_weight,
+                         bc_weight=bc_weight, critic=critic)
+    o["g"], = LN.flat_grads([nets["actor"]], o, fill=NAN)
     torch.cuda.synchronize()
     return o
 
@@ -316,16 +259,7 @@ TRAINER = dict(n_envs=256, envs_per_group=128, hidden=64, n_hidden=2, batch=128,
 
 
 def _learner_state(tr):
-    out = {k: v.params.clone() for k, v in tr.td3.networks().items()}
-    for k, o in (("actor", tr.td3.actor_optimizer), ("critic1", tr.td3.critic_optimizer_1),
-                 ("critic2", tr.td3.critic_optimizer_2)):
-        out[k + "_m"], out[k + "_v"] = o.m.clone(), o.v.clone()
-    out["ring"] = tr.replay.rows.clone()
-    return out
-
-
-def _same(a, b):
-    return all(torch.equal(a[k], b[k]) for k in a) and a.keys() == b.keys()
+    return snapshot(tr, "moments")
 
 
 @pytest.fixture(scope="module")

@@ -16,68 +16,33 @@ import pytest
 import torch
 
 import bcq_ref as Q
+import launches as LN
 import mlp_ref as R
-from test_gpu_width_depth import _device_net, _equal_nan, _ids, _nan
+from gpu_support import equal_nan as _equal_nan, ids as _ids, nav  # noqa: F401
+from launches import nan as _nan
+from pop_support import equal_tree as _equal_tree, member_state, same as _same, snapshot
 
 pytestmark = pytest.mark.gpu
 DEV = R.DEV
-SEED = 1707366464
+NAN = float("nan")
 W_BC = 0.5   # bc_weight of the cases (q_weight 1)
-
-
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    import nav as navpkg
-    return navpkg
 
 
 @functools.lru_cache(maxsize=None)
 def _setup(hidden, nh, B, b_demo):
-    from nav._lib import NavReplay
     case = Q.bcq_case(hidden, nh, B, b_demo)
-    nets = {n: _device_net(case["layers"][n], *((2, 2) if n == "actor" else (4, 1)), hidden, nh)
-            for n in ("actor", "cr0")}
-    dev = dict(rows=case["rows"].to(DEV).contiguous(), idx_a=case["idx_a"].to(DEV))
-    dev["rd"] = NavReplay(dev["rows"].data_ptr(), Q.N_ROWS)
-    return case, nets, dev
+    return (case, *LN.device_epoch(case))
 
 
 def _launch(key, b_demo, bc_weight, form, grads=False):
     """nav_td3_actor_rows_bcq (form "bcq") or nav_td3_actor_rows_bc ("bc") of case `key` into
     NaN-prefilled buffers (keep_part prefilled with -1), q_weight 1; grads: then nav_mlp_wgrad and
     nav_grad_reduce into the actor's flat gradient `g`."""
-    from nav._lib import descs, lib, parr, ptr, stream_handle
     _, nets, dev = _setup(*key)
-    B = key[2]
-    L, s = lib(), stream_handle()
-    actor, cr = nets["actor"], nets["cr0"]
-    hp, nh = actor.hp, actor.n_hidden
-    mid = actor.middle_layers()
-    nblk = L.nav_mlp_row_blocks(B)
-    o = dict(batch=_nan(B, 8), q=_nan(B), da=_nan(B, 2), acts=_nan(nh, B, hp), dz=_nan(nh, B, hp),
-             ma=actor.mask_buffer(B), mc=cr.mask_buffer(B), part=_nan(nblk), q_demo=_nan(B),
-             keep_part=torch.full((nblk,), -1, dtype=torch.int32, device=DEV),
-             es=_nan(nblk, L.nav_mlp_edge_count(2, 2, hp, nh)), nblk=nblk)
-    head = (C.byref(actor.desc()), C.byref(cr.desc()), C.byref(dev["rd"]), Q.N_ROWS, B,
-            ptr(dev["idx_a"]), SEED & 0xFFFFFFFF, SEED >> 32, 3, b_demo, 1.0, bc_weight,
-            ptr(o["batch"]), ptr(o["q"]), ptr(o["da"]), ptr(o["part"]))
-    tail = (ptr(o["acts"]), mid, ptr(o["dz"]), mid, ptr(o["ma"]), ptr(o["mc"]), ptr(o["es"]), s)
-    if form == "bcq":
-        assert L.nav_td3_actor_rows_bcq(*head, ptr(o["q_demo"]), ptr(o["keep_part"]), *tail) == 0
-    else:
-        assert L.nav_td3_actor_rows_bc(*head, *tail) == 0
+    o = LN.actor_rows(nets, dev, key[2], form=form, fill=NAN, b_demo=b_demo, q_weight=1.0,
+                     bc_weight=bc_weight)
     if grads:
-        splits = int(L.nav_mlp_wgrad_splits(1, 2, hp, nh, B))
-        hs = _nan(splits, max(4, L.nav_mlp_hidden_count(hp, nh)))
-        assert L.nav_mlp_wgrad(descs(actor), 1, B, ptr(o["batch"]), 8, 0, parr(o["acts"]),
-                               parr(o["dz"]), parr(o["da"]), 2, parr(o["ma"]), parr(hs), splits,
-                               s) == 0
-        o["g"] = _nan(actor.count)
-        assert L.nav_grad_reduce(C.byref(actor.desc()), ptr(hs), splits, ptr(o["es"]), nblk,
-                                 ptr(o["g"]), s) == 0
+        o["g"], = LN.flat_grads([nets["actor"]], o, fill=NAN)
     torch.cuda.synchronize()
     return o
 
@@ -241,16 +206,7 @@ ON = dict(demo_fraction=0.25, bc_weight=1.0)
 
 
 def _learner_state(tr):
-    out = {k: v.params.clone() for k, v in tr.td3.networks().items()}
-    for k, o in (("actor", tr.td3.actor_optimizer), ("critic1", tr.td3.critic_optimizer_1),
-                 ("critic2", tr.td3.critic_optimizer_2)):
-        out[k + "_m"], out[k + "_v"] = o.m.clone(), o.v.clone()
-    out["ring"] = tr.replay.storage.clone()
-    return out
-
-
-def _same(a, b):
-    return a.keys() == b.keys() and all(torch.equal(a[k], b[k]) for k in a)
+    return snapshot(tr, "moments", ring="storage")
 
 
 def _steps(tr, n=3):
@@ -297,20 +253,10 @@ POP = dict(hidden=64, n_hidden=2, batch=128, updates_per_step=2, seed=1234, envs
 
 
 def _member_state(tr, m):
-    r = tr.rings[m]
-    return {"rows": r.storage.clone(), "position": r.position, "size": r.size,
-            "td3": tr.td3[m].state_dict()}
-
-
-def _equal_tree(a, b, path=""):
-    if isinstance(a, dict):
-        assert a.keys() == b.keys(), path
-        for k in a:
-            _equal_tree(a[k], b[k], f"{path}/{k}")
-    elif torch.is_tensor(a):
-        assert torch.equal(a.cpu(), b.cpu()), path
-    else:
-        assert a == b, path
+    """Member m's ring with its tail and its learner (the envs of a mixed population's member are
+    not compared with a lone trainer's here)."""
+    s = member_state(tr, m, tail=True)
+    return {**s["replay"], "td3": s["td3"]}
 
 
 def test_population_members_learner_takes_the_key(nav):

@@ -23,6 +23,7 @@ import torch
 
 import cem_ref
 from conftest import golden
+from gpu_support import ulps_f32
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -77,12 +78,6 @@ def fptr(field):
 def stream():
     from nav._lib import stream_handle
     return stream_handle()
-
-
-def ulps_f32(a, b):
-    a = np.asarray(a, np.float32).view(np.int32).astype(np.int64)
-    b = np.asarray(b, np.float32).view(np.int32).astype(np.int64)
-    return np.abs(a - b)
 
 
 # ---------------------------------------------------------------- nav_rollout

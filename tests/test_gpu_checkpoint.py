@@ -6,23 +6,15 @@ import os
 import pytest
 import torch
 
+from pop_support import snapshot
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 
 
 def _snapshot(tr):
-    e = tr.env
-    snap = {k: getattr(e, k).clone() for k in tr.ENV_STATE}
-    snap["replay"] = tr.replay.rows.clone()
-    for name, net in tr.td3.networks().items():
-        snap[name] = net.params.clone()
-        snap[name + "_packed"] = net.packed.clone()
-    for name, o in (("adam_a", tr.td3.actor_optimizer), ("adam_c1", tr.td3.critic_optimizer_1),
-                    ("adam_c2", tr.td3.critic_optimizer_2)):
-        snap[name + "_m"], snap[name + "_v"] = o.m.clone(), o.v.clone()
-    snap["action"] = tr.action.clone()
-    return snap
+    return snapshot(tr, "env", "packed", "moments", "action")
 
 
 @pytest.mark.parametrize("demos", [True, False])

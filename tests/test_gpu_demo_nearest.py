@@ -14,6 +14,7 @@ import torch
 
 import demo_ref as D
 from conftest import golden
+from gpu_support import nav  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,15 +22,6 @@ DEV = "cuda"
 SENT = -777.25   # sentinel of rows, reward_out and block_stats (exact in float32)
 N, EPG = D.N_ENVS, D.EPG
 F_STUCK, F_DEMO = D.F_STUCK, D.F_DEMO
-
-
-@pytest.fixture(scope="module")
-def nav():
-    import nav as navpkg
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    return navpkg
 
 
 def dev(a, dtype=None):

@@ -13,6 +13,8 @@ import torch
 
 import demo_reset_ref as D
 import mlp_ref as R
+from gpu_support import nav  # noqa: F401
+from pop_support import same as _same, snapshot
 
 pytestmark = pytest.mark.gpu
 DEV = R.DEV
@@ -20,15 +22,6 @@ SEED = 1707366464
 SLO, SHI = SEED & 0xFFFFFFFF, SEED >> 32
 SOA = ("state", "goal", "region", "hist", "meta", "plan_index", "path_length", "episodes",
        "noise_scale")
-
-
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    import nav as navpkg
-    return navpkg
 
 
 def bits64(a):
@@ -294,19 +287,8 @@ def test_exploit_hands_the_probability_to_the_clone(nav, pop_pair):
 
 
 # ---------------------------------------------------------------- the trainer
-def _params(tr):
-    return {k: n.params.clone() for k, n in tr.networks().items()}
-
-
 def _snapshot(tr):
-    s = _params(tr.td3)
-    s["ring"] = tr.replay.rows.clone()
-    s.update({k: getattr(tr.env, k).clone() for k in tr.ENV_STATE})
-    return s
-
-
-def _same(a, b):
-    return all(torch.equal(a[k], b[k]) for k in a) and set(a) == set(b)
+    return snapshot(tr, "env")
 
 
 def test_off_means_off(nav):

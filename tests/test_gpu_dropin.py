@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from conftest import golden
+from gpu_support import ulps_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -52,13 +53,6 @@ def test_environment_dynamics_and_step_api(navmods):
         assert np.max(np.abs(after - d["step"][i])) < 1e-11
 
 
-def ulps_f32(a, b):
-    """|a - b| in float32 ulps (both finite float32 of one sign: positions in the world)."""
-    a = np.asarray(a, np.float32).view(np.int32).astype(np.int64)
-    b = np.asarray(b, np.float32).view(np.int32).astype(np.int64)
-    return np.abs(a - b)
-
-
 TRACES = ["trace.npz", "trace_branches.npz", "trace_branches_field.npz"]
 
 
@@ -98,7 +92,7 @@ def test_robot_replays_reference_trace(navmods, name):
     the goal, the path's end and their coincidences with the stuck check; there the Robot's
     goal_reached / stuck_flag are also compared right after process_transition and a goal
     row's reward exactly."""
-    from test_oracle_branches_cpu import check_goal_row
+    from trace_support import check_goal_row
     environment, robot = navmods
     t, env, state, rb = _trace_setup(environment, robot, name)
     scripted = "step_goal" in t.files

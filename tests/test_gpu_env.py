@@ -11,19 +11,11 @@ import pytest
 import torch
 
 from conftest import golden
+from gpu_support import nav, sync_oracle as _sync_oracle  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-
-
-@pytest.fixture(scope="module")
-def nav():
-    import nav as navpkg
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    return navpkg
 
 
 def field_of(speed, angle):
@@ -203,18 +195,6 @@ def test_env_init_and_reset_bit_exact_vs_oracle(nav, orc, n, epg):
         assert np.array_equal(st[e], vec_reset_one(p, e, 5, region[e]))
 
 
-def _sync_oracle(env, ost):
-    ost.state[:] = env.state.cpu().numpy()
-    ost.goal[:] = env.goal.cpu().numpy()
-    ost.region[:] = env.region.cpu().numpy()
-    ost.hist[:] = env.hist.cpu().numpy().transpose(1, 0, 2)
-    ost.meta[:] = env.meta.cpu().numpy().astype(np.uint32)
-    ost.plan_index[:] = env.plan_index.cpu().numpy()
-    ost.path_length[:] = env.path_length.cpu().numpy()
-    ost.episodes[:] = env.episodes.cpu().numpy()
-    ost.noise_scale[:] = env.noise_scale.cpu().numpy()
-
-
 def test_agent_step_vs_oracle_per_step(nav, orc):
     """Fused tick (nav_agent_step + nav_demo_reward) vs the oracle's restated tick, re-synced from
     the device state before every step so every step is compared on identical inputs."""
@@ -309,7 +289,7 @@ def _replay_reference_trace(name, form):
     (done = push_d, goal, stuck, ended = the reference's next tick is a reset) and a goal row's
     reward exactly (50, or 0 when stuck on the same step)."""
     from nav.vec_env import ReplayRing, VecEnv
-    from test_oracle_branches_cpu import check_goal_row, want_flags
+    from trace_support import check_goal_row, want_flags
     t = golden(name)
     env = VecEnv(1, field_of(t["speed"], t["angle"]), init=False)
     types = t["tick_type"]

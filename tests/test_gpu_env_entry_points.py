@@ -11,19 +11,12 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import nav  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 N = 65
-
-
-@pytest.fixture(scope="module")
-def nav():
-    import nav as navpkg
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    return navpkg
 
 
 def test_check_if_stuck_vs_oracle(nav, orc):

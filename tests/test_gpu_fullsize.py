@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import sync_oracle as _sync_oracle
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -25,14 +27,6 @@ def trainer():
     return tr
 
 
-_MIRROR = ("state", "goal", "region", "meta", "plan_index", "path_length", "episodes",
-           "noise_scale")
-
-
-def _sync_oracle(env, ost):
-    for k in _MIRROR:
-        getattr(ost, k)[:] = getattr(env, k).cpu().numpy()
-    ost.hist[:] = env.hist.cpu().numpy().transpose(1, 0, 2)
 
 
 def test_bench_config_tick_subset_vs_oracle(trainer, orc):
@@ -219,7 +213,7 @@ def test_td3_update_at_bench_config_vs_oracle():
     """The learner pinned at the bench configuration (2x256 actor/critics, batch 32 768, the
     bench's 2 epochs per step: critic, actor + Polyak, critic): TD3.td3_update with injected batch
     indices and smoothing noise vs the oracle's restatement of robot.py:258-398 on the CPU."""
-    from test_gpu_shared_policy import make_learner, replay_rows, ring_of
+    from pop_support import make_learner, replay_rows, ring_of
     from oracle.td3_oracle import TD3Oracle, make_mlp_params
     B, hidden, nh, epochs = 32768, 256, 2, 2
     sizes = lambda di, do: [di] + [hidden] * nh + [do]  # noqa: E731
@@ -302,7 +296,7 @@ def test_learner_gradients_at_bench_config_vs_oracle():
     the kernels' own ReLU decisions (pre-activations within rounding of 0 may branch either way).
     Every entry within rtol 1e-4; scale <g, g_ref> / |g_ref|^2 within 1e-5 of 1 per net."""
     from mlp_ref import relu_bits
-    from test_gpu_shared_policy import make_learner, replay_rows, ring_of
+    from pop_support import make_learner, replay_rows, ring_of
     from oracle.td3_oracle import TD3Oracle, make_mlp_params
     B, hidden, nh = 32768, 256, 2
     sizes = lambda di, do: [di] + [hidden] * nh + [do]  # noqa: E731

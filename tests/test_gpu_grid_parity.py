@@ -12,18 +12,11 @@ import pytest
 import torch
 
 from conftest import golden
+from gpu_support import nav  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 SEED = (0x5A17 << 32) | 424242  # seed_hi != 0
-
-
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    torch.cuda.set_device(0)
 
 
 def _assert_blocks(name, err, scale, bound):
@@ -157,7 +150,7 @@ def test_branch_trace_at_bench_grid(nav):
     counters and row equal env 0's bit for bit (one comparison on the device per tick), so a
     workgroup or band that forms a branch differently shows."""
     from nav.vec_env import ReplayRing, VecEnv, make_field
-    from test_oracle_branches_cpu import check_goal_row, step_ticks, want_flags
+    from trace_support import check_goal_row, step_ticks, want_flags
     t = golden("trace_branches.npz")
     n = 65536
     env = VecEnv(n, make_field(t["speed"], t["angle"], DEV), envs_per_group=n, init=False)

@@ -15,20 +15,13 @@ import numpy as np
 import pytest
 import torch
 
+import launches as LN
 from conftest import golden
+from gpu_support import nav  # noqa: F401
 from mlp_ref import (DEV, _assert_images_exact, _f64_forward, _grad_flat_vs_autograd,  # noqa: F401
                      make_net, relu_bits, split_gemm_row_errors, torch_mlp)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    import nav as navpkg
-    return navpkg
 
 
 @pytest.mark.parametrize("d_in,d_out,hidden,nh", [(2, 2, 200, 3), (4, 1, 200, 3), (2, 2, 256, 2),
@@ -445,6 +438,21 @@ def test_td3_update_vs_oracle_and_reference(nav):
             np.testing.assert_allclose(v, g[name + "_val"][k], rtol=0, atol=3e-7)
 
 
+def _fused_case(hidden, nh, seed0, cap, ring_seed):
+    """(nets by launches' names with seeds seed0 .., dev): six distinct nets and a ring of
+    `cap` random rows (done ~ 10 %) the fused launches draw from themselves (no idx, no eps)."""
+    from nav._lib import NavReplay
+    nets = {name: make_net(*LN.KIND[name], hidden, nh, seed0 + k)[0]
+            for k, name in enumerate(("ta", "tc0", "tc1", "cr0", "cr1", "actor"))}
+    g = torch.Generator().manual_seed(ring_seed)
+    rows = torch.randn(cap, 8, generator=g) * 10
+    rows[:, 7] = (torch.rand(cap, generator=g) < 0.1).float()
+    rows = rows.to(DEV)
+    dev = dict(rows=rows, idx=None, idx_a=None, eps=None, size=cap,
+               rd=NavReplay(rows.data_ptr(), cap))
+    return nets, dev
+
+
 # 16 421 rows: the 64-row (RT = 2) form the bench's batch runs
 # 333 / 2048: 32-row blocks with L2 warmer rows beside them (<= 128 compute workgroups); 4097:
 # 32-row blocks without (129); 16421: 64-row blocks
@@ -454,23 +462,16 @@ def test_fused_row_kernels_match_unfused(nav, hidden, nh, B):
     """nav_td3_critic_rows / nav_td3_actor_rows (one launch each) produce bit-identical batches,
     targets, dq, losses, ReLU bits, dL/da and edge partials to the per-network kernels they
     fuse (same device code, same order)."""
-    from nav._lib import NavReplay, descs, lib, parr, ptr, stream_handle
+    from nav._lib import descs, lib, parr, ptr, stream_handle
     from nav.mlp import forward
     L = lib()
     s = stream_handle()
-    ta, _ = make_net(2, 2, hidden, nh, 61)
-    tc = [make_net(4, 1, hidden, nh, 62 + k)[0] for k in range(2)]
-    cr = [make_net(4, 1, hidden, nh, 64 + k)[0] for k in range(2)]
-    actor, _ = make_net(2, 2, hidden, nh, 66)
+    nets, dev = _fused_case(hidden, nh, 61, 5000, 9)
+    ta, tc, cr, actor = nets["ta"], [nets["tc0"], nets["tc1"]], [nets["cr0"], nets["cr1"]], \
+        nets["actor"]
+    rd = dev["rd"]
     hp = ta.hp
-    cap = 5000
-    g = torch.Generator().manual_seed(9)
-    rows = torch.randn(cap, 8, generator=g) * 10
-    rows[:, 7] = (torch.rand(cap, generator=g) < 0.1).float()
-    rows = rows.to(DEV)
-    rd = NavReplay(rows.data_ptr(), cap)
-    seed, counter = 1707366464, 3
-    slo, shi = seed & 0xFFFFFFFF, seed >> 32
+    cap, counter, slo, shi = 5000, 3, LN.SLO, LN.SHI
     mid = cr[0].middle_layers()
     nblk = L.nav_mlp_row_blocks(B)
     f = lambda *sh: torch.zeros(*sh, device=DEV)  # noqa: E731
@@ -479,7 +480,7 @@ def test_fused_row_kernels_match_unfused(nav, hidden, nh, B):
     def critic_bufs():
         return dict(batch=f(B, 8), dq=[f(B), f(B)], lp=f(2, nblk), es=[f(nblk, ec), f(nblk, ec)],
                     acts=[f(nh, B, hp), f(nh, B, hp)], masks=[cr[0].mask_buffer(B) for _ in range(2)])
-    u, v = critic_bufs(), critic_bufs()
+    u = critic_bufs()
     # unfused: sample, target actor with smoothing, twin targets, online twin with the TD loss
     L.nav_replay_sample(C.byref(rd), cap, B, None, slo, shi, 2 * counter, ptr(u["batch"]), s)
     tgt_in, q1t, q2t = f(B, 4), f(B), f(B)
@@ -490,18 +491,11 @@ def test_fused_row_kernels_match_unfused(nav, hidden, nh, B):
     L.nav_td3_critic_forward(descs(*cr), B, ptr(u["batch"]), 8, 0, ptr(u["batch"]), ptr(q1t),
                              ptr(q2t), 0.99, parr(*u["dq"]), parr(u["lp"][0], u["lp"][1]),
                              parr(*u["es"]), parr(*u["acts"]), mid, parr(*u["masks"]), s)
-    L.nav_td3_critic_rows(C.byref(ta.desc()), descs(*tc), descs(*cr), C.byref(rd), cap, B, None,
-                          slo, shi, counter, None, 0.2, 0.5, 5.0, 0.99, ptr(v["batch"]),
-                          parr(*v["dq"]), parr(v["lp"][0], v["lp"][1]), parr(*v["es"]),
-                          parr(*v["acts"]), mid, parr(*v["masks"]), 0, None, 0, -1, s)
+    v = LN.critic_rows(nets, dev, B, fill=0.0, row_backward=0)
     # the same launch with each online critic's row backward fused in, against the separate
     # nav_mlp_backward of the unfused path (same device code, same order: same bits)
-    w = critic_bufs()
-    wdz = [f(nh, B, cr[0].hp), f(nh, B, cr[0].hp)]
-    L.nav_td3_critic_rows(C.byref(ta.desc()), descs(*tc), descs(*cr), C.byref(rd), cap, B, None,
-                          slo, shi, counter, None, 0.2, 0.5, 5.0, 0.99, ptr(w["batch"]),
-                          parr(*w["dq"]), parr(w["lp"][0], w["lp"][1]), parr(*w["es"]),
-                          parr(*w["acts"]), mid, parr(*w["masks"]), 1, parr(*wdz), mid, -1, s)
+    w = LN.critic_rows(nets, dev, B, fill=0.0)
+    wdz = w["dz"]
     udz = [f(nh, B, cr[0].hp), f(nh, B, cr[0].hp)]
     ues = [u["es"][0].clone(), u["es"][1].clone()]
     L.nav_mlp_backward(descs(*cr), 2, B, parr(*u["dq"]), 1, parr(*u["masks"]), ptr(u["batch"]),
@@ -526,7 +520,7 @@ def test_fused_row_kernels_match_unfused(nav, hidden, nh, B):
     def actor_bufs():
         return dict(batch=f(B, 8), q=f(B), da=f(B, 2), acts=f(nh, B, hp), dz=f(nh, B, hp),
                     ma=actor.mask_buffer(B), mc=cr[0].mask_buffer(B), es=f(nblk, eca))
-    u, v = actor_bufs(), actor_bufs()
+    u = actor_bufs()
     L.nav_replay_sample(C.byref(rd), cap, B, None, slo, shi, 2 * counter + 1, ptr(u["batch"]), s)
     forward([actor], u["batch"], 8, 0, [u["batch"]], 8, 2, B, acts=[u["acts"]], save_mask=save,
             masks=[u["ma"]])
@@ -539,10 +533,7 @@ def test_fused_row_kernels_match_unfused(nav, hidden, nh, B):
     L.nav_mlp_backward(descs(actor), 1, B, parr(da), 4, parr(u["ma"]), ptr(u["batch"]), 8, 0,
                        parr(u["acts"][nh - 1]), parr(u["dz"]), actor.middle_layers(), None,
                        parr(u["es"]), s)
-    L.nav_td3_actor_rows(C.byref(actor.desc()), C.byref(cr[0].desc()), C.byref(rd), cap, B, None,
-                         slo, shi, counter, ptr(v["batch"]), ptr(v["q"]), ptr(v["da"]),
-                         ptr(v["acts"]), save, ptr(v["dz"]), actor.middle_layers(), ptr(v["ma"]),
-                         ptr(v["mc"]), ptr(v["es"]), s)
+    v = LN.actor_rows(nets, dev, B, form="plain", fill=0.0, save_mask=save)
     torch.cuda.synchronize()
     assert torch.equal(u["batch"][:, :2], v["batch"][:, :2])
     assert torch.equal(u["batch"][:, 4:], v["batch"][:, 4:])
@@ -561,34 +552,10 @@ def test_critic_rows_split_twins_bit_identical(nav, hidden, nh, B):
     small-batch form) and in one (grid.y = 1) at the same batch: batch rows, dq, loss partials,
     edge slabs, saved rows, ReLU bits and dz all bit-equal (same per-critic device code and
     order; the twin workgroups only repeat the target passes, and only y == 0 writes `batch`)."""
-    from nav._lib import NavReplay, descs, lib, parr, ptr, stream_handle
-    L = lib()
-    s = stream_handle()
-    ta, _ = make_net(2, 2, hidden, nh, 161)
-    tc = [make_net(4, 1, hidden, nh, 162 + k)[0] for k in range(2)]
-    cr = [make_net(4, 1, hidden, nh, 164 + k)[0] for k in range(2)]
-    hp = ta.hp
-    cap = 3000
-    g = torch.Generator().manual_seed(19)
-    rows = torch.randn(cap, 8, generator=g) * 10
-    rows[:, 7] = (torch.rand(cap, generator=g) < 0.1).float()
-    rows = rows.to(DEV)
-    rd = NavReplay(rows.data_ptr(), cap)
-    mid = cr[0].middle_layers()
-    nblk = L.nav_mlp_row_blocks(B)
-    f = lambda *sh: torch.full(sh, float("nan"), device=DEV)  # noqa: E731
-    ec = L.nav_mlp_edge_count(4, 1, hp, nh)
-    out = {}
-    for split in (True, False):
-        o = dict(batch=f(B, 8), dq=[f(B), f(B)], lp=f(2, nblk), es=[f(nblk, ec), f(nblk, ec)],
-                 acts=[f(nh, B, hp), f(nh, B, hp)], dz=[f(nh, B, hp), f(nh, B, hp)],
-                 masks=[cr[0].mask_buffer(B) for _ in range(2)])
-        assert L.nav_td3_critic_rows(
-            C.byref(ta.desc()), descs(*tc), descs(*cr), C.byref(rd), cap, B, None, 1707366464,
-            0, 5, None, 0.2, 0.5, 5.0, 0.99, ptr(o["batch"]), parr(*o["dq"]),
-            parr(o["lp"][0], o["lp"][1]), parr(*o["es"]), parr(*o["acts"]), mid,
-            parr(*o["masks"]), 1, parr(*o["dz"]), mid, int(split), s) == 0
-        out[split] = o
+    nets, dev = _fused_case(hidden, nh, 161, 3000, 19)
+    mid = nets["cr0"].middle_layers()
+    out = {split: LN.critic_rows(nets, dev, B, fill=float("nan"), split=int(split), counter=5)
+           for split in (True, False)}
     torch.cuda.synchronize()
     a, b = out[True], out[False]
     assert torch.equal(a["batch"], b["batch"])

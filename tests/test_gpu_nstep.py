@@ -15,26 +15,19 @@ import numpy as np
 import pytest
 import torch
 
+import launches as LN
 import mlp_ref as R
 import nstep_ref as N
 import per_ref as P
-from test_nstep_cpu import BAD, CALLS
+from gpu_support import nav  # noqa: F401
+from nstep_args import BAD, CALLS
+from pop_support import moments as _moments, params as _params, same as _same, snapshot
 
 pytestmark = pytest.mark.gpu
 DEV = R.DEV
-SEED = 1707366464
-SLO, SHI = SEED & 0xFFFFFFFF, SEED >> 32
+SEED, SLO, SHI = LN.SEED, LN.SLO, LN.SHI
 GAMMA = 0.99
 COUNTER = 5
-
-
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    import nav as navpkg
-    return navpkg
 
 
 def bits(a):
@@ -216,45 +209,23 @@ def test_ticks_write_the_marks(nav, form):
 
 
 # ---------------------------------------------------------------- the critic on staged rows
-def _critic(nets, rd, size, idx, eps, B, counter=3):
-    """nav_td3_critic_rows on the ring descriptor `rd` into zeroed buffers."""
-    from nav._lib import descs, lib, parr, ptr, stream_handle
-    L = lib()
-    cr = [nets["cr0"], nets["cr1"]]
-    hp, nh = cr[0].hp, cr[0].n_hidden
-    mid = cr[0].middle_layers()
-    nblk = L.nav_mlp_row_blocks(B)
-    ec = L.nav_mlp_edge_count(4, 1, hp, nh)
-    z = lambda *s: torch.zeros(*s, device=DEV)  # noqa: E731
-    o = dict(batch=z(B, 8), dq=[z(B), z(B)], lp=z(2, nblk), es=[z(nblk, ec), z(nblk, ec)],
-             acts=[z(nh, B, hp), z(nh, B, hp)], dz=[z(nh, B, hp), z(nh, B, hp)],
-             masks=[c.mask_buffer(B) for c in cr])
-    L.nav_td3_critic_rows(C.byref(nets["ta"].desc()), descs(nets["tc0"], nets["tc1"]), descs(*cr),
-                          C.byref(rd), size, B, ptr(idx), SLO, SHI, counter, ptr(eps), 0.2, 0.5,
-                          5.0, GAMMA, ptr(o["batch"]), parr(*o["dq"]),
-                          parr(o["lp"][0], o["lp"][1]), parr(*o["es"]), parr(*o["acts"]), mid,
-                          parr(*o["masks"]), 1, parr(*o["dz"]), mid, -1, stream_handle())
-    return o
+def _critic(nets, rd, idx, eps, B):
+    """nav_td3_critic_rows on the ring descriptor `rd` of B rows into zeroed buffers."""
+    return LN.critic_rows(nets, dict(idx=idx, eps=eps), B, fill=0.0, rd=rd, size=B, gamma=GAMMA)
 
 
 @pytest.mark.parametrize("hidden", [64, 256])
 def test_critic_sees_the_n_step_target(nav, hidden):
     from nav._lib import NavReplay, lib, ptr, stream_handle
-    from nav.mlp import DeviceMLP
     nh, B, n_step, stride, position = 2, 257, 3, 7, 123
     case = R.epoch_case(hidden, nh, B)
-    nets = {}
-    for name, layers in case["layers"].items():
-        d_in, d_out = (2, 2) if name in ("ta", "actor", "atgt") else (4, 1)
-        nets[name] = DeviceMLP(d_in, d_out, hidden, nh, DEV).load(
-            [(W.numpy(), b.numpy()) for W, b in layers])
+    nets, dev = LN.device_epoch(case)
     ring = case["rows"].numpy()
     rng = np.random.default_rng(11)
     cut = ((ring[:, 7] != 0) | (rng.random(R.RING) < 0.15)).astype(np.uint8)
     idx = case["idx"].numpy()
-    rows, dcut = case["rows"].to(DEV).contiguous(), torch.from_numpy(cut).to(DEV)
-    eps = case["eps"].to(DEV).contiguous()
-    didx = case["idx"].to(DEV)
+    dcut = torch.from_numpy(cut).to(DEV)
+    rows, eps, didx = dev["rows"], dev["eps"], dev["idx"]
     # the device's staging, then the critic launch on the staged rows in order
     staged = torch.full((B, 8), float("nan"), device=DEV)
     steps = torch.zeros(B, dtype=torch.int32, device=DEV)
@@ -262,11 +233,11 @@ def test_critic_sees_the_n_step_target(nav, hidden):
                          stride, n_step, GAMMA, B, ptr(didx), SLO, SHI, 3, ptr(staged),
                          ptr(steps), stream_handle())
     iota = torch.arange(B, dtype=torch.int64, device=DEV)
-    got = _critic(nets, NavReplay(staged.data_ptr(), B), B, iota, eps, B)
+    got = _critic(nets, NavReplay(staged.data_ptr(), B), iota, eps, B)
     # nav_td3_critic_rows directly on a ring whose rows are the restatement's staged rows
     want_rows, want_steps = N.rows(ring, cut, R.RING, position, stride, n_step, GAMMA, idx)
     href = torch.from_numpy(want_rows).to(DEV)
-    ref = _critic(nets, NavReplay(href.data_ptr(), B), B, iota, eps, B)
+    ref = _critic(nets, NavReplay(href.data_ptr(), B), iota, eps, B)
     torch.cuda.synchronize()
     assert np.array_equal(steps.cpu().numpy(), want_steps) and want_steps.max() == n_step
     assert len(set(want_steps.tolist())) == n_step
@@ -302,22 +273,6 @@ def test_critic_sees_the_n_step_target(nav, hidden):
 
 
 # ---------------------------------------------------------------- the trainer
-def _params(tr):
-    return {k: n.params.clone() for k, n in tr.networks().items()}
-
-
-def _moments(t):
-    out = {}
-    for name, o in (("a", t.actor_optimizer), ("c1", t.critic_optimizer_1),
-                    ("c2", t.critic_optimizer_2)):
-        out[name + "m"], out[name + "v"] = o.m.clone(), o.v.clone()
-    return out
-
-
-def _same(a, b):
-    return all(torch.equal(a[k], b[k]) for k in a) and set(a) == set(b)
-
-
 def test_off_means_off(nav):
     from nav.trainer import VecTrainer
     snaps = []
@@ -328,11 +283,7 @@ def test_off_means_off(nav):
         torch.cuda.synchronize()
         assert tr.replay.cut is None and tr.td3.nstep_launches == 0 and not tr.td3.nstep_on()
         assert not hasattr(tr.td3, "staged") and not hasattr(tr.td3, "idx_iota")
-        s = _params(tr.td3)
-        s.update(_moments(tr.td3))
-        s["ring"] = tr.replay.rows.clone()
-        s.update({k: getattr(tr.env, k).clone() for k in tr.ENV_STATE})
-        snaps.append(s)
+        snaps.append(snapshot(tr, "moments", "env"))
         sd = tr.state_dict()
         assert "n_step" not in sd["meta"] and "cut" not in sd["replay"]
     assert _same(*snaps)

@@ -9,67 +9,11 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import nav  # noqa: F401
+from pop_support import (CAP, DEV, FILL, copied_state, differences, equal_tree, learner_state,
+                         leaves, make_ring, make_td3, member_state, state_member, workspace)
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-CAP, FILL = 4096, 3000
-
-
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    import nav as navpkg
-    return navpkg
-
-
-# ---- as tests/test_gpu_population_learner.py builds its learners and rings
-def make_td3(m, hidden, nh, B, epochs, splits=None):
-    """Member m's learner: its own seed (weights, sampling, smoothing noise) and its own value of
-    every per-member hyper-parameter."""
-    from nav import config as K
-    from nav.td3 import TD3
-    cfg = K.TD3Config(actor_lr=1e-4 * (m + 1), critic_lr=1e-3 / (m + 1), gamma=0.99 - 0.01 * m,
-                      tau=0.005 * (m + 1), policy_noise=0.2 + 0.05 * m, noise_clip=0.5 - 0.05 * m,
-                      policy_update_delay=2, max_action=5.0 - 0.5 * m, batch_size=B,
-                      num_epochs=epochs, net=K.NetConfig(hidden=hidden, n_hidden=nh))
-    return TD3(cfg, device=DEV, seed=1000 + 17 * m, wgrad_splits=splits)
-
-
-def make_ring(m):
-    from nav.vec_env import ReplayRing
-    g = torch.Generator().manual_seed(500 + m)
-    rows = torch.randn(CAP, 8, generator=g)
-    rows[:, 7] = (torch.rand(CAP, generator=g) < 0.1).float()  # done in {0, 1}
-    rows[FILL:] = 0.0
-    r = ReplayRing(CAP, DEV)
-    r.rows.copy_(rows.to(DEV))
-    r.advance(FILL)
-    return r
-
-
-def differences(a, b, path="", out=None):
-    """The paths at which two trees of dicts / tensors / values differ (bitwise)."""
-    out = [] if out is None else out
-    if isinstance(a, dict):
-        assert a.keys() == b.keys(), path
-        for k in a:
-            differences(a[k], b[k], f"{path}/{k}", out)
-    elif isinstance(a, (list, tuple)):
-        assert len(a) == len(b), path
-        for i, (x, y) in enumerate(zip(a, b)):
-            differences(x, y, f"{path}/{i}", out)
-    elif torch.is_tensor(a):
-        if not torch.equal(a, b):
-            out.append(path)
-    elif a != b:
-        out.append(path)
-    return out
-
-
-def equal_tree(a, b, path=""):
-    bad = differences(a, b, path)
-    assert not bad, bad
 
 
 # ---- 1. the summary
@@ -122,52 +66,6 @@ def test_summary_against_torch(nav, epm):
 
 
 # ---- 2. the exploit launch
-NETS = ("actor", "critic1", "critic2", "target_actor", "target_critic1", "target_critic2")
-
-
-def state_member(t, ring):
-    """The learner state of one TD3 and its ring as a nav_td3_member; everything else null."""
-    from nav._lib import NavTd3Member
-    e = NavTd3Member()
-    e.actor, e.target_actor = t.actor_network.desc(), t.target_actor.desc()
-    e.critics[0], e.critics[1] = t.critic_network_1.desc(), t.critic_network_2.desc()
-    e.target_critics[0] = t.target_critic_network_1.desc()
-    e.target_critics[1] = t.target_critic_network_2.desc()
-    e.replay = ring.desc()
-    oa, oc1, oc2 = t.actor_optimizer, t.critic_optimizer_1, t.critic_optimizer_2
-    e.m_actor, e.v_actor = oa.m.data_ptr(), oa.v.data_ptr()
-    e.m_critic[0], e.m_critic[1] = oc1.m.data_ptr(), oc2.m.data_ptr()
-    e.v_critic[0], e.v_critic[1] = oc1.v.data_ptr(), oc2.v.data_ptr()
-    return e
-
-
-def copied_state(t):
-    """What a pair copies apart from the ring, as device clones."""
-    nets = t.networks()
-    opts = {"actor": t.actor_optimizer, "critic1": t.critic_optimizer_1,
-            "critic2": t.critic_optimizer_2}
-    c = lambda x: x.detach().clone()  # noqa: E731
-    return {"params": {k: c(nets[k].params) for k in NETS},
-            "packed": {k: c(nets[k].packed) for k in NETS},
-            "m": {k: c(o.m) for k, o in opts.items()},
-            "v": {k: c(o.v) for k, o in opts.items()}}
-
-
-def workspace(t):
-    c = lambda x: x.detach().clone()  # noqa: E731
-    return {"batch": c(t.batch), "batch2": c(t.batch2), "dq1": c(t.dq1), "dq2": c(t.dq2),
-            "da": c(t.da), "q": c(t.q1), "loss_part": c(t.loss_part), "grad_a": c(t.grad_a),
-            "grad_c": c(t.grad_c), "eslab1": c(t.eslab1), "hslab": c(t.hslab)}
-
-
-def leaves(tree, path=""):
-    if isinstance(tree, dict):
-        for k, v in tree.items():
-            yield from leaves(v, f"{path}/{k}")
-    else:
-        yield path, tree
-
-
 SHAPES = [(64, 2), (200, 3), (32, 1), (256, 2)]
 
 
@@ -272,8 +170,6 @@ def test_state_table_past_one_chunk(nav):
 
 
 # ---- 3 .. 6. the trainer
-SOA = ("state", "goal", "region", "hist", "meta", "plan_index", "path_length", "episodes",
-       "noise_scale")
 TRAINER = dict(envs_per_member=128, hidden=64, n_hidden=2, batch=128, updates_per_step=2,
                seed=1234, envs_per_group=128, replay_capacity=1024, demos=False)
 
@@ -281,21 +177,6 @@ TRAINER = dict(envs_per_member=128, hidden=64, n_hidden=2, batch=128, updates_pe
 def trainer(members, **kw):
     from nav.population import PopulationTrainer
     return PopulationTrainer(members, device=DEV, **{**TRAINER, **kw})
-
-
-def learner_state(t):
-    return {**copied_state(t), "work": workspace(t), "update_counter": t.update_counter,
-            "t": [o.step_count for o in (t.actor_optimizer, t.critic_optimizer_1,
-                                         t.critic_optimizer_2)]}
-
-
-def member_state(tr, m):
-    sl = tr.member_slice(m)
-    env = {k: (getattr(tr.env, k)[:, sl] if k == "hist" else getattr(tr.env, k)[sl]).cpu()
-           for k in SOA}
-    r = tr.rings[m]
-    return {"env": env, "replay": {"rows": r.rows.cpu(), "position": r.position, "size": r.size},
-            "td3": tr.td3[m].state_dict(), "steps": tr.steps}
 
 
 @pytest.mark.parametrize("learner", ["members", "batched"])
@@ -308,20 +189,22 @@ def test_a_clone_continues_as_its_source(nav, learner):
     for _ in range(4):
         tr.step()
     torch.cuda.synchronize()
-    a, b = learner_state(tr.td3[0]), learner_state(tr.td3[1])
+    a, b = learner_state(tr.td3[0], work=True), learner_state(tr.td3[1], work=True)
     differ = differences(a, b)
-    for kind in ("params", "packed", "m", "v"):
+    for kind in ("params", "packed"):
         for k in a[kind]:
             assert f"/{kind}/{k}" in differ, (kind, k)
+    for k in a["adam"]:
+        assert f"/adam/{k}/m" in differ and f"/adam/{k}/v" in differ, k
     assert "/work/batch" in differ and not torch.equal(tr.rings[0].rows, tr.rings[1].rows)
     assert tr.td3[0].update_counter == 8
     tr.exploit([0], [1], copy_replay=True)
     tr.learn()
     torch.cuda.synchronize()
     assert tr.td3[0].update_counter == 10
-    equal_tree(learner_state(tr.td3[1]), learner_state(tr.td3[0]))
+    equal_tree(learner_state(tr.td3[1], work=True), learner_state(tr.td3[0], work=True))
     assert torch.equal(tr.rings[0].rows, tr.rings[1].rows)
-    assert differences(learner_state(tr.td3[0]), a)  # and the learners moved
+    assert differences(learner_state(tr.td3[0], work=True), a)  # and the learners moved
 
 
 def test_the_others_are_untouched(nav):

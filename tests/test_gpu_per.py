@@ -14,23 +14,16 @@ import numpy as np
 import pytest
 import torch
 
+import launches as LN
 import mlp_ref as R
 import per_ref as P
+from gpu_support import nav, ulps_f32  # noqa: F401
+from pop_support import params as _params, same as _same, snapshot
 
 pytestmark = pytest.mark.gpu
 DEV = R.DEV
-SEED = 1707366464
-SLO, SHI = SEED & 0xFFFFFFFF, SEED >> 32
+SEED, SLO, SHI = LN.SEED, LN.SLO, LN.SHI
 MAXP = P.MAX_PRI
-
-
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    import nav as navpkg
-    return navpkg
 
 
 # ---------------------------------------------------------------- the priority store
@@ -69,9 +62,7 @@ class Store:
 
 def ulps(a, b):
     """|a - b| in f32 steps, for non-negative finite floats"""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    assert np.isfinite(a).all() and np.isfinite(b).all() and (a >= 0).all() and (b >= 0).all()
-    return np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))
+    return ulps_f32(a, b, nonneg=True)
 
 
 RINGS = [(3000, 2500), (3000, 1), (4096, 4096), ((1 << 20) + 37, (1 << 20) + 5)]
@@ -272,10 +263,6 @@ def test_update_non_finite_errors_store_no_zero(nav):
 SHAPES = [(64, 2), (256, 2), (200, 3)]
 
 
-def _zeros(*shape):
-    return torch.zeros(*shape, device=DEV)
-
-
 _SETUPS = {}
 
 
@@ -283,65 +270,20 @@ def _setup(hidden, nh, B):
     """mlp_ref.epoch_case on the device (nets, ring, injected idx and eps), built once."""
     key = (hidden, nh, B)
     if key not in _SETUPS:
-        from nav._lib import NavReplay
-        from nav.mlp import DeviceMLP
         case = R.epoch_case(hidden, nh, B)
-        nets = {}
-        for name, layers in case["layers"].items():
-            d_in, d_out = (2, 2) if name in ("ta", "actor", "atgt") else (4, 1)
-            nets[name] = DeviceMLP(d_in, d_out, hidden, nh, DEV).load(
-                [(W.numpy(), b.numpy()) for W, b in layers])
-        dev = dict(rows=case["rows"].to(DEV).contiguous(), idx=case["idx"].to(DEV),
-                   eps=case["eps"].to(DEV).contiguous())
-        dev["rd"] = NavReplay(dev["rows"].data_ptr(), R.RING)
         _SETUPS.clear()  # one case's tensors at a time
-        _SETUPS[key] = (case, nets, dev)
+        _SETUPS[key] = (case, *LN.device_epoch(case))
     return _SETUPS[key]
 
 
-def _rows(nets, dev, B, w=None, split=-1, row_backward=1):
-    """nav_td3_critic_rows (w None) or nav_td3_critic_rows_w into zeroed buffers."""
-    from nav._lib import descs, lib, parr, ptr, stream_handle
-    L = lib()
-    cr = [nets["cr0"], nets["cr1"]]
-    hp, nh = cr[0].hp, cr[0].n_hidden
-    mid = cr[0].middle_layers()
-    nblk = L.nav_mlp_row_blocks(B)
-    ec = L.nav_mlp_edge_count(4, 1, hp, nh)
-    o = dict(batch=_zeros(B, 8), dq=[_zeros(B), _zeros(B)], lp=_zeros(2, nblk),
-             es=[_zeros(nblk, ec), _zeros(nblk, ec)], acts=[_zeros(nh, B, hp), _zeros(nh, B, hp)],
-             dz=[_zeros(nh, B, hp), _zeros(nh, B, hp)], masks=[c.mask_buffer(B) for c in cr],
-             td=[torch.full((B,), float("nan"), device=DEV) for _ in range(2)])
-    head = (C.byref(nets["ta"].desc()), descs(nets["tc0"], nets["tc1"]), descs(*cr),
-            C.byref(dev["rd"]), R.RING, B, ptr(dev["idx"]), SLO, SHI, 3, ptr(dev["eps"]), 0.2, 0.5,
-            5.0, 0.99, ptr(o["batch"]), parr(*o["dq"]), parr(o["lp"][0], o["lp"][1]),
-            parr(*o["es"]), parr(*o["acts"]), mid, parr(*o["masks"]), row_backward,
-            parr(*o["dz"]), mid, split)
-    if w is None:
-        L.nav_td3_critic_rows(*head, stream_handle())
-    else:
-        L.nav_td3_critic_rows_w(*head, ptr(w), parr(*o["td"]), stream_handle())
-    return o
+def _rows(nets, dev, B, **kw):
+    """nav_td3_critic_rows (no w) or nav_td3_critic_rows_w into zeroed buffers."""
+    return LN.critic_rows(nets, dev, B, fill=0.0, **kw)
 
 
 def _flat_grads(nets, o, B):
     """nav_mlp_wgrad -> nav_grad_reduce of a rows launch: both critics' flat gradients."""
-    from nav._lib import descs, lib, parr, ptr, stream_handle
-    L = lib()
-    s = stream_handle()
-    cr = [nets["cr0"], nets["cr1"]]
-    hp, nh = cr[0].hp, cr[0].n_hidden
-    splits = int(L.nav_mlp_wgrad_splits(2, 1, hp, nh, B))
-    hs = [_zeros(splits, max(4, L.nav_mlp_hidden_count(hp, nh))) for _ in range(2)]
-    L.nav_mlp_wgrad(descs(*cr), 2, B, ptr(o["batch"]), 8, 0, parr(*o["acts"]), parr(*o["dz"]),
-                    parr(*o["dq"]), 1, parr(*o["masks"]), parr(*hs), splits, s)
-    out = []
-    for k in range(2):
-        g = torch.full((cr[k].count,), float("nan"), device=DEV)
-        L.nav_grad_reduce(C.byref(cr[k].desc()), ptr(hs[k]), splits, ptr(o["es"][k]),
-                          o["lp"].shape[1], ptr(g), s)
-        out.append(g)
-    return out
+    return LN.flat_grads([nets["cr0"], nets["cr1"]], o, fill=0.0)
 
 
 def _random_w(B, seed=0):
@@ -387,7 +329,7 @@ def test_random_weights(nav, hidden, nh, B):
     fwd = _rows(nets, dev, B, w=w, row_backward=0)  # the Wo / bo partials alone
     # nav_mlp_backward of the weighted dq on the plain launch's masks: dz rows and W0 / bias
     # partials, into the forward-only launch's edge slabs
-    udz = [_zeros(nh, B, cr[0].hp), _zeros(nh, B, cr[0].hp)]
+    udz = [torch.zeros(nh, B, cr[0].hp, device=DEV) for _ in range(2)]
     L.nav_mlp_backward(descs(*cr), 2, B, parr(*wtd["dq"]), 1, parr(*plain["masks"]),
                        ptr(plain["batch"]), 8, 0, None, parr(*udz), mid, None, parr(*fwd["es"]),
                        stream_handle())
@@ -486,14 +428,6 @@ TRAINER = dict(n_envs=256, hidden=64, batch=128, replay_capacity=1024, envs_per_
 PER = dict(per_alpha=0.6, per_beta=0.4, per_eps=1e-6)
 
 
-def _params(tr):
-    return {k: n.params.clone() for k, n in tr.td3.networks().items()}
-
-
-def _same(a, b):
-    return all(torch.equal(a[k], b[k]) for k in a) and set(a) == set(b)
-
-
 def test_off_means_off(nav):
     from nav.trainer import VecTrainer
     snaps = []
@@ -505,10 +439,7 @@ def test_off_means_off(nav):
         assert tr.replay.pri is None and tr.replay.sums is None and tr.replay.stat is None
         assert tr.td3.per_launches == 0 and not tr.td3.per_on()
         assert not hasattr(tr.td3, "w_per")
-        s = _params(tr)
-        s["ring"] = tr.replay.rows.clone()
-        s.update({k: getattr(tr.env, k).clone() for k in tr.ENV_STATE})
-        snaps.append(s)
+        snaps.append(snapshot(tr, "env"))
         assert "per_alpha" not in tr.state_dict()["meta"]
     assert _same(*snaps)
 
@@ -691,12 +622,6 @@ def _filled_ring():
     return ring
 
 
-def _sd_same(a, b):
-    if isinstance(a, dict):
-        return set(a) == set(b) and all(_sd_same(a[k], b[k]) for k in a)
-    return torch.equal(a, b) if torch.is_tensor(a) else a == b
-
-
 @pytest.mark.parametrize("field,value", [("per_alpha", 0.6), ("n_step", 3)])
 def test_a_mode_switched_on_later_gets_its_workspace(nav, field, value):
     """The workspace is keyed by what it allocates for. A: a learner built with the mode off runs
@@ -723,6 +648,6 @@ def test_a_mode_switched_on_later_gets_its_workspace(nav, field, value):
     torch.cuda.synchronize()
     assert a.per_launches == b.per_launches == (6 if field == "per_alpha" else 0)
     assert a.nstep_launches == b.nstep_launches == (2 if field == "n_step" else 0)
-    assert _sd_same(a.state_dict(), b.state_dict()) and not _sd_same(mid, b.state_dict())
+    assert _same(a.state_dict(), b.state_dict()) and not _same(mid, b.state_dict())
     assert torch.equal(ring_a.pri, ring_b.pri) and torch.equal(ring_a.stat, ring_b.stat)
     assert (field == "per_alpha") == (len(set(ring_a.pri.cpu().tolist())) > 2)

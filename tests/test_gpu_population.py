@@ -8,6 +8,9 @@ import pytest
 import torch
 
 from conftest import golden
+from gpu_support import nav  # noqa: F401
+from pop_support import (SOA, clone_out, equal_tree as _equal_tree, make_actor, member_state,
+                         random_field, random_starts)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -16,32 +19,7 @@ N = P * EPM
 TICKS = 40
 T_TEST = 12
 SEED = 77
-SOA = ("state", "goal", "region", "hist", "meta", "plan_index", "path_length", "episodes",
-       "noise_scale")
 STEP_OUT = ("next_state", "goal_term", "flags", "block_stats")
-
-
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    import nav as navpkg
-    return navpkg
-
-
-def random_field(seed):
-    from nav.vec_env import make_field
-    rng = np.random.default_rng(seed)
-    speed = rng.uniform(0.05, 0.95, (100, 100)).astype(np.float32)
-    angle = rng.uniform(0.0, 1.0, (100, 100)).astype(np.float32)
-    return make_field(speed, angle, DEV)
-
-
-def make_actor(hidden, nh, seed):
-    from nav.mlp import DeviceMLP
-    from oracle.td3_oracle import make_mlp_params
-    return DeviceMLP(2, 2, hidden, nh, DEV).load(make_mlp_params(seed, [2] + [hidden] * nh + [2]))
 
 
 def member_params(m, distinct=True, **extra):
@@ -60,8 +38,8 @@ def member_params(m, distinct=True, **extra):
 def make_env(n, demos, field=None):
     """n envs in groups of EPG, path_length0 = 6; demos: each group's demo set is a shifted copy
     of the reference demonstration set, indexed."""
-    from nav.vec_env import VecEnv
-    env = VecEnv(n, field if field is not None else random_field(5), seed=SEED,
+    from nav.vec_env import VecEnv, make_field
+    env = VecEnv(n, field if field is not None else make_field(*random_field(5), DEV), seed=SEED,
                  envs_per_group=EPG, demo_flag=demos, device=DEV, path_length0=6)
     if demos:
         demo = golden("trace.npz")["demo_set"]
@@ -117,7 +95,7 @@ def tick_case(hidden, demos):
     from nav.vec_env import ReplayRing
     env = make_env(N, demos)
     start = snapshot(env)
-    actors = [make_actor(hidden, 2, 31 + m) for m in range(P)]
+    actors = [make_actor(hidden, 2, 31 + m)[0] for m in range(P)]
     params = [member_params(m) for m in range(P)]
     cap = P * EPM  # 3 ticks of a member: the rings wrap 13 times in 40 ticks
     ring_rows = torch.zeros(P, cap, 8, dtype=torch.float32, device=DEV)
@@ -189,7 +167,7 @@ def test_tick_identical_members(nav):
     ticks = 10
     env = make_env(N, True)
     start = snapshot(env)
-    actor = make_actor(64, 2, 31)
+    actor = make_actor(64, 2, 31)[0]
     p = member_params(0, distinct=False)
     cap = P * EPM
     ring_rows = torch.zeros(P, cap, 8, dtype=torch.float32, device=DEV)
@@ -236,7 +214,7 @@ def test_tick_table_past_one_chunk(nav):
     n = P7 * epm
     env = make_env(n, True)
     start = snapshot(env)
-    actors = [make_actor(32, 1, 31 + m) for m in range(P7)]
+    actors = [make_actor(32, 1, 31 + m)[0] for m in range(P7)]
     params = [member_params(m % 3, demo_factor=10.0 + 5.0 * m) for m in range(P7)]
     cap = 3 * epm
     ring_rows = torch.zeros(P7, cap, 8, dtype=torch.float32, device=DEV)
@@ -280,20 +258,6 @@ def test_tick_table_past_one_chunk(nav):
     assert not torch.equal(ends[5]["state"], ends[6]["state"])
 
 
-def random_starts(env, seed):
-    """test_gpu_test_rollout.py's form: uniform starts in the world; every 5th env one unit from
-    its goal, so that some rows stop at the first step while their workgroup goes on."""
-    g = torch.Generator().manual_seed(seed)
-    st = torch.rand(env.n, 2, generator=g, dtype=torch.float64) * 98.0
-    near = torch.arange(env.n) % 5 == 0
-    st[near] = env.goal.cpu()[near] + torch.tensor([0.6, -0.8], dtype=torch.float64)
-    return st.clamp_(0.0, 98.0).to(DEV)
-
-
-def clone_out(out):
-    return {k: v.clone() for k, v in out.items()}
-
-
 _test_cases = {}
 
 
@@ -305,7 +269,7 @@ def rollout_case(hidden, epm):
         return _test_cases[key]
     from nav.population import PopulationTable
     env = make_env(P * epm, False)
-    actors = [make_actor(hidden, 2, 31 + m) for m in range(P)]
+    actors = [make_actor(hidden, 2, 31 + m)[0] for m in range(P)]
     params = [member_params(m, goal_threshold=2.0 + 4.0 * m, max_action=5.0 - m)
               for m in range(P)]
     pop = PopulationTable(actors, params, None, epm)
@@ -345,32 +309,6 @@ def test_test_rollout(nav, hidden, epm):
     assert int((g["steps"] == 1).sum()) > 0 and int((g["reached"] == 0).sum()) > 0
     r0, r2 = c["refs"][0]["given"]["reached"], c["refs"][2]["given"]["reached"]
     assert not torch.equal(r0, r2)
-
-
-def _equal_tree(a, b, path=""):
-    if isinstance(a, dict):
-        assert a.keys() == b.keys(), path
-        for k in a:
-            _equal_tree(a[k], b[k], f"{path}/{k}")
-    elif isinstance(a, (list, tuple)):
-        assert len(a) == len(b), path
-        for i, (x, y) in enumerate(zip(a, b)):
-            _equal_tree(x, y, f"{path}/{i}")
-    elif torch.is_tensor(a):
-        assert torch.equal(a, b), path
-    else:
-        assert a == b, path
-
-
-def member_state(tr, m):
-    """Everything member m's next step reads, as host tensors: its env slice, its ring and its
-    learner (every parameter, Adam moment and counter)."""
-    sl = tr.member_slice(m)
-    env = {k: (getattr(tr.env, k)[:, sl] if k == "hist" else getattr(tr.env, k)[sl]).cpu()
-           for k in SOA}
-    r = tr.rings[m]
-    return {"env": env, "replay": {"rows": r.rows.cpu(), "position": r.position, "size": r.size},
-            "td3": tr.td3[m].state_dict(), "steps": tr.steps}
 
 
 TRAINER = dict(hidden=64, n_hidden=2, batch=128, updates_per_step=2, seed=1234,

@@ -10,20 +10,14 @@ import torch
 import bc_ref as BR
 import mlp_ref as R
 import pop_bc_ref as PB
-from test_gpu_population_learner import equal_tree, learner_state
+import pop_support as PS
+from gpu_support import nav  # noqa: F401
+from launches import device_net as _device_net
+from pop_support import equal_tree, learner_state
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 CAP, FILL, N_TAIL, COUNTER = PB.CAP, PB.FILL, PB.N_TAIL, PB.COUNTER
-
-
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    import nav as navpkg
-    return navpkg
 
 
 def _nan_fill(t):
@@ -33,20 +27,9 @@ def _nan_fill(t):
         t.fill_(0x5A5A if t.dtype == torch.int16 else -1)
 
 
-def make_ring(m, storage=None):
-    """A ring of CAP rows filled to FILL with a tail of N_TAIL rows behind it: fixed random rows
-    (or `storage`), the unfilled rows zero."""
-    from nav.vec_env import ReplayRing
-    r = ReplayRing(CAP, DEV, tail=N_TAIL)
-    if storage is None:
-        g = torch.Generator().manual_seed(500 + m)
-        storage = torch.randn(CAP + N_TAIL, 8, generator=g) * 10
-        storage[:, 7] = (torch.rand(CAP + N_TAIL, generator=g) < 0.1).float()
-        storage[FILL:CAP] = 0.0
-        storage[CAP:, 7] = 0.0
-    r.storage.copy_(storage.to(DEV))
-    r.advance(FILL)
-    return r
+def tailed_ring(m, storage=None):
+    """pop_support.make_ring with a tail of N_TAIL demonstration rows behind the ring."""
+    return PS.make_ring(m, tail=N_TAIL, storage=storage, cap=CAP, fill=FILL)
 
 
 class KernelCase:
@@ -61,7 +44,6 @@ class KernelCase:
         from nav._lib import NavTd3MemberBc, lib, ptr
         from nav.population import PopulationLearner
         from nav.td3 import TD3
-        from test_gpu_width_depth import _device_net
         P = self.P = len(b_demos)
         self.B, self.b_demos = B, list(b_demos)
         self.weights = list(weights or [(1.0, 0.5 if b else 0.0) for b in b_demos])
@@ -77,7 +59,7 @@ class KernelCase:
             t._static()
             t.update_counter = COUNTER
             self.td3.append(t)
-            self.rings.append(make_ring(m, storage))
+            self.rings.append(tailed_ring(m, storage))
         self.learner = PopulationLearner(self.td3, self.rings)
         assert self.learner.bc_table is None  # no member's cfg has the feature on
         self.learner.inject(idx_critic=[t.idx_c for t in self.td3],
@@ -264,15 +246,15 @@ def test_actor_rows_bc_pop_vs_fp64(nav, first_case):
 LEARN = [(0.25, 1.0, 1.0), (0.5, 0.5, 0.25), (1.0, 3.0, 0.5)]  # demo_fraction, bc_weight, q_weight
 
 
-def make_td3(m, B, epochs, splits=None):
+def bc_td3(m, B, epochs, splits=None):
+    """pop_support.make_td3 at hidden 64 x 2 with member m's demonstration weights, pop_bc_ref's
+    seed, and the default smoothing noise and action bound for every member."""
     from nav import config as K
-    from nav.td3 import TD3
     f, w, q = LEARN[m]
-    cfg = K.TD3Config(actor_lr=1e-4 * (m + 1), critic_lr=1e-3 / (m + 1), gamma=0.99 - 0.01 * m,
-                      tau=0.005 * (m + 1), policy_update_delay=2, batch_size=B, num_epochs=epochs,
-                      demo_fraction=f, bc_weight=w, q_weight=q,
-                      net=K.NetConfig(hidden=64, n_hidden=2))
-    return TD3(cfg, device=DEV, seed=PB.member_seed(m), wgrad_splits=splits)
+    d = K.TD3Config()
+    return PS.make_td3(m, 64, 2, B, epochs, splits, seed=PB.member_seed(m), demo_fraction=f,
+                       bc_weight=w, q_weight=q, policy_noise=d.policy_noise,
+                       noise_clip=d.noise_clip, max_action=d.max_action)
 
 
 def bc_state(t):
@@ -290,8 +272,8 @@ def test_epochs_distinct_members(nav):
     batched run's split counts; one mix launch per epoch for the whole population."""
     from nav.population import PopulationLearner
     B, P = 128, 3
-    rings = [make_ring(m) for m in range(P)]
-    td3 = [make_td3(m, B, 3) for m in range(P)]
+    rings = [tailed_ring(m) for m in range(P)]
+    td3 = [bc_td3(m, B, 3) for m in range(P)]
     learner = PopulationLearner(td3, rings)
     assert learner.bc_table is not None
     learner.update(3)
@@ -299,7 +281,7 @@ def test_epochs_distinct_members(nav):
     got = [bc_state(t) for t in td3]
     assert learner.mix_launches == 3 and all(t.mix_launches == 0 for t in td3)
     for m in range(P):
-        t = make_td3(m, B, 3, splits=learner.wgrad_splits)
+        t = bc_td3(m, B, 3, splits=learner.wgrad_splits)
         t.td3_update(rings[m], 3)
         torch.cuda.synchronize()
         assert t.mix_launches == 3 and t.b_demo() == round(LEARN[m][0] * B)
@@ -312,22 +294,14 @@ def test_epochs_distinct_members(nav):
 
 
 # ---- the trainer ----
-SOA = ("state", "goal", "region", "hist", "meta", "plan_index", "path_length", "episodes",
-       "noise_scale")
 TRAINER = dict(hidden=64, n_hidden=2, batch=128, updates_per_step=2, seed=1234,
                envs_per_group=128)
 ON = {"demo_fraction": 0.25, "bc_weight": 1.0}
 
 
-def member_state(tr, m):
+def tailed_state(tr, m):
     """Member m's env slice, its ring with the tail and its learner."""
-    sl = tr.member_slice(m)
-    env = {k: (getattr(tr.env, k)[:, sl] if k == "hist" else getattr(tr.env, k)[sl]).cpu()
-           for k in SOA}
-    r = tr.rings[m]
-    return {"env": env,
-            "replay": {"rows": r.storage.cpu(), "position": r.position, "size": r.size},
-            "td3": tr.td3[m].state_dict(), "steps": tr.steps}
+    return PS.member_state(tr, m, tail=True)
 
 
 def run_trainer(members, steps=3, **kw):
@@ -336,7 +310,7 @@ def run_trainer(members, steps=3, **kw):
     for _ in range(steps):
         tr.step()
     torch.cuda.synchronize()
-    return tr, [member_state(tr, m) for m in range(len(members))]
+    return tr, [tailed_state(tr, m) for m in range(len(members))]
 
 
 @pytest.fixture(scope="module")
@@ -441,7 +415,7 @@ def test_exploit_hands_over_the_values_and_keeps_the_tail(nav, pair_run):
             tr.step()
         torch.cuda.synchronize()
         assert torch.equal(tr.rings[1].tail, tail)
-        ends.append([member_state(tr, m) for m in range(2)])
+        ends.append([tailed_state(tr, m) for m in range(2)])
     equal_tree(ends[0], ends[1])
     with pytest.raises(KeyError, match="cannot be explored"):
         tr.exploit([0], [1], explore={"demo_fraction": (0.0, 1.0)})

@@ -7,88 +7,11 @@ TD3 with the same weight-gradient split counts."""
 import pytest
 import torch
 
+from gpu_support import nav  # noqa: F401
+from pop_support import (DEV, equal_tree, injection, learner_state, make_ring, make_td3,
+                         member_state)
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-CAP, FILL = 4096, 3000
-
-
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    import nav as navpkg
-    return navpkg
-
-
-def make_td3(m, hidden, nh, B, epochs, splits=None):
-    """Member m's learner: its own seed (weights, sampling, smoothing noise) and its own value of
-    every per-member hyper-parameter."""
-    from nav import config as K
-    from nav.td3 import TD3
-    cfg = K.TD3Config(actor_lr=1e-4 * (m + 1), critic_lr=1e-3 / (m + 1), gamma=0.99 - 0.01 * m,
-                      tau=0.005 * (m + 1), policy_noise=0.2 + 0.05 * m, noise_clip=0.5 - 0.05 * m,
-                      policy_update_delay=2, max_action=5.0 - 0.5 * m, batch_size=B,
-                      num_epochs=epochs, net=K.NetConfig(hidden=hidden, n_hidden=nh))
-    return TD3(cfg, device=DEV, seed=1000 + 17 * m, wgrad_splits=splits)
-
-
-def make_ring(m):
-    from nav.vec_env import ReplayRing
-    g = torch.Generator().manual_seed(500 + m)
-    rows = torch.randn(CAP, 8, generator=g)
-    rows[:, 7] = (torch.rand(CAP, generator=g) < 0.1).float()  # done in {0, 1}
-    rows[FILL:] = 0.0
-    r = ReplayRing(CAP, DEV)
-    r.rows.copy_(rows.to(DEV))
-    r.advance(FILL)
-    return r
-
-
-def learner_state(t):
-    """Everything the issue's comparison names, as device clones."""
-    nets = t.networks()
-    opts = {"actor": t.actor_optimizer, "critic1": t.critic_optimizer_1,
-            "critic2": t.critic_optimizer_2}
-    c = lambda x: x.detach().clone()  # noqa: E731
-    return {"params": {k: c(v.params) for k, v in nets.items()},
-            "packed": {k: c(v.packed) for k, v in nets.items()},
-            "adam": {k: {"m": c(o.m), "v": c(o.v), "t": o.step_count} for k, o in opts.items()},
-            "batch": c(t.batch), "batch2": c(t.batch2), "dq1": c(t.dq1), "dq2": c(t.dq2),
-            "loss_part": c(t.loss_part), "q": c(t.q1), "da": c(t.da),
-            "update_counter": t.update_counter}
-
-
-def differences(a, b, path="", out=None):
-    """The paths at which two trees of dicts / tensors / values differ (bitwise)."""
-    out = [] if out is None else out
-    if isinstance(a, dict):
-        assert a.keys() == b.keys(), path
-        for k in a:
-            differences(a[k], b[k], f"{path}/{k}", out)
-    elif isinstance(a, (list, tuple)):
-        assert len(a) == len(b), path
-        for i, (x, y) in enumerate(zip(a, b)):
-            differences(x, y, f"{path}/{i}", out)
-    elif torch.is_tensor(a):
-        if not torch.equal(a, b):
-            out.append(path)
-    elif a != b:
-        out.append(path)
-    return out
-
-
-def equal_tree(a, b, path=""):
-    bad = differences(a, b, path)
-    assert not bad, bad
-
-
-def injection(m, B):
-    g = torch.Generator().manual_seed(900 + m)
-    ic = torch.randint(0, FILL, (B,), generator=g, dtype=torch.int64).to(DEV)
-    ia = torch.randint(0, FILL, (B,), generator=g, dtype=torch.int64).to(DEV)
-    eps = torch.randn(B, 2, generator=g).to(DEV)
-    return ic, ia, eps
 
 
 def run_case(P, hidden, nh, B, epochs, inject=False):
@@ -174,22 +97,11 @@ def test_coresident_grid(nav):
 
 
 # ---- the trainer
-SOA = ("state", "goal", "region", "hist", "meta", "plan_index", "path_length", "episodes",
-       "noise_scale")
 TRAINER = dict(hidden=64, n_hidden=2, batch=128, updates_per_step=2, seed=1234,
                envs_per_group=128)
 
 
 equal_any = equal_tree
-
-
-def member_state(tr, m):
-    sl = tr.member_slice(m)
-    env = {k: (getattr(tr.env, k)[:, sl] if k == "hist" else getattr(tr.env, k)[sl]).cpu()
-           for k in SOA}
-    r = tr.rings[m]
-    return {"env": env, "replay": {"rows": r.rows.cpu(), "position": r.position, "size": r.size},
-            "td3": tr.td3[m].state_dict(), "steps": tr.steps}
 
 
 def run_trainer(members, **kw):

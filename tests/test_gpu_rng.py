@@ -17,16 +17,10 @@ import pytest
 import torch
 from scipy import stats
 
+from gpu_support import nav  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    torch.cuda.set_device(0)
 
 
 def _zero_net(d_in, d_out, hidden=64, nh=2):
@@ -235,7 +229,7 @@ def test_td3_update_on_philox_path_vs_oracle(nav, orc):
     Measured on MI355X: max |diff| vs the oracle actor 7.5e-9, critic 1 1.5e-8, critic 2 3.0e-8,
     targets <= 1.2e-10; (i) bit-identical to (u); losses equal to 5e-8 relative."""
     from mlp_ref import relu_bits
-    from test_gpu_shared_policy import make_learner, replay_rows
+    from pop_support import make_learner, replay_rows
     from nav.vec_env import ReplayRing
     from oracle.td3_oracle import TD3Oracle, make_mlp_params
     B, hidden, nh, epochs, cap, fill, c0 = 16421, 256, 2, 2, 50000, 40000, 5

@@ -26,21 +26,21 @@ import pytest
 import torch
 
 import bc_ref as BR
+import launches as LN
 import mlp_ref as R
-import test_gpu_width_depth as W
+import pop_support as T
+from gpu_support import equal_nan, nav  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = R.DEV
 LOG = R.ParityLog()
+NAN = float("nan")
 
 
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    import nav as navpkg
-    yield navpkg
+@pytest.fixture(scope="module", autouse=True)
+def _parity_log():
+    """At the end of the module: the worst figures of (5), where NAV_SCALE_PARITY names a file."""
+    yield
     path = os.environ.get("NAV_SCALE_PARITY")
     if path:
         LOG.write(path)
@@ -126,20 +126,6 @@ def test_packed_images_carry_the_layer_shift(nav, shape, name):
 
 
 # ---- (4) the fused launches under joint shifts ----
-def _epoch_setup(case):
-    """test_gpu_width_depth._epoch_setup for a given epoch_case."""
-    from nav._lib import NavReplay
-    hidden, nh = case["hidden"], case["nh"]
-    nets = {}
-    for name, layers in case["layers"].items():
-        d_in, d_out = (2, 2) if name in ("ta", "actor", "atgt") else (4, 1)
-        nets[name] = W._device_net(layers, d_in, d_out, hidden, nh)
-    dev = dict(rows=case["rows"].to(DEV).contiguous(), idx=case["idx"].to(DEV),
-               idx_a=case["idx_a"].to(DEV), eps=case["eps"].to(DEV).contiguous())
-    dev["rd"] = NavReplay(dev["rows"].data_ptr(), case["rows"].shape[0])
-    return nets, dev
-
-
 def _assert_batch(got, base, K):
     """A sampled batch under the joint shift: the reward column times 2^K, the rest equal."""
     keep = [0, 1, 2, 3, 5, 6, 7]
@@ -150,47 +136,34 @@ def _assert_batch(got, base, K):
 def _critic_launches(hidden, nh, B, K):
     """nav_td3_critic_rows -> nav_mlp_wgrad (nav_mlp_wgrad_splits) -> nav_grad_reduce of
     epoch_case(hidden, nh, B, K) as test_fused_critic_epoch_vs_fp64 issues them: CPU tensors."""
-    from nav._lib import descs, lib, parr, ptr, stream_handle
-    L, s = lib(), stream_handle()
-    nets, dev = _epoch_setup(R.epoch_case(hidden, nh, B, K))
+    nets, dev = LN.device_epoch(R.epoch_case(hidden, nh, B, K))
     cr = [nets["cr0"], nets["cr1"]]
-    hp = cr[0].hp
-    o = W._critic_rows(nets, dev, B, 0)
-    splits = int(L.nav_mlp_wgrad_splits(2, 1, hp, nh, B))
-    hs = [W._nan(splits, max(4, L.nav_mlp_hidden_count(hp, nh))) for _ in range(2)]
-    assert L.nav_mlp_wgrad(descs(*cr), 2, B, ptr(o["batch"]), 8, 0, parr(*o["acts"]),
-                           parr(*o["dz"]), parr(*o["dq"]), 1, parr(*o["masks"]), parr(*hs),
-                           splits, s) == 0
-    grads = [W._nan(c.count) for c in cr]
-    for k in range(2):
-        assert L.nav_grad_reduce(C.byref(cr[k].desc()), ptr(hs[k]), splits, ptr(o["es"][k]),
-                                 o["lp"].shape[1], ptr(grads[k]), s) == 0
+    o = LN.critic_rows(nets, dev, B, fill=NAN, split=0)
+    grads = LN.flat_grads(cr, o, fill=NAN)
     torch.cuda.synchronize()
     q = dict(batch=o["batch"].cpu(), masks=[m.cpu() for m in o["masks"]])
     for k in range(2):
         q[f"c{k}_dq"], q[f"c{k}_loss"] = o["dq"][k].cpu(), o["lp"][k].cpu()
-        q.update({f"c{k}_{n}": t for n, t in R.flat_grad_tensors(grads[k].cpu(), 4, 1, hidden, hp,
-                                                                 nh).items()})
+        q.update({f"c{k}_{n}": t for n, t in R.flat_grad_tensors(grads[k].cpu(), 4, 1, hidden,
+                                                                 cr[0].hp, nh).items()})
+    return q
+
+
+def _actor_quantities(o, g, hidden, hp, nh):
+    q = dict(batch=o["batch"].cpu(), masks=[o["ma"].cpu(), o["mc"].cpu()], a_q=o["q"].cpu(),
+             a_da=o["da"].cpu())
+    q.update({f"a_{n}": t for n, t in R.flat_grad_tensors(g.cpu(), 2, 2, hidden, hp, nh).items()})
     return q
 
 
 def _actor_launches(hidden, nh, B, K):
     """nav_td3_actor_rows -> nav_mlp_wgrad -> nav_grad_reduce as test_fused_actor_epoch_vs_fp64
     issues them: CPU tensors."""
-    from nav._lib import lib, ptr, stream_handle
-    L = lib()
-    nets, dev = _epoch_setup(R.epoch_case(hidden, nh, B, K))
-    actor = nets["actor"]
-    o = W._actor_rows(nets, dev, B)
-    g = W._nan(actor.count)
-    assert L.nav_grad_reduce(C.byref(actor.desc()), ptr(o["hs"]), o["splits"], ptr(o["es"]),
-                             o["nblk"], ptr(g), stream_handle()) == 0
+    nets, dev = LN.device_epoch(R.epoch_case(hidden, nh, B, K))
+    o = LN.actor_rows(nets, dev, B, form="plain", fill=NAN)
+    g, = LN.flat_grads([nets["actor"]], o, fill=NAN)
     torch.cuda.synchronize()
-    q = dict(batch=o["batch"].cpu(), masks=[o["ma"].cpu(), o["mc"].cpu()], a_q=o["q"].cpu(),
-             a_da=o["da"].cpu())
-    q.update({f"a_{n}": t for n, t in R.flat_grad_tensors(g.cpu(), 2, 2, hidden, actor.hp,
-                                                          nh).items()})
-    return q
+    return _actor_quantities(o, g, hidden, nets["actor"].hp, nh)
 
 
 _epochs = {}
@@ -258,39 +231,31 @@ def test_actor_rows_bc_is_shift_equivariant(nav):
     """nav_td3_actor_rows_bc at (150, 2), B = 100, 7 demonstration rows, q_weight 1 and the BC
     weight 0.5 * 2^K, so that both terms of da carry K: q, da and the gradients shift, the
     blocks' BC sums (of (pi - a)^2, unweighted) and the sampled rows do not."""
-    import test_gpu_bc as TB
-    from nav._lib import NavReplay
     hidden, nh, B, bd = 150, 2, 100, 7
     runs = {}
     for K in (None,) + R.SCALE_KS:
-        case = BR.bc_case(hidden, nh, B, bd, K=K)
-        nets = {n: W._device_net(case["layers"][n], *((2, 2) if n == "actor" else (4, 1)), hidden,
-                                 nh) for n in ("actor", "cr0")}
-        dev = dict(rows=case["rows"].to(DEV).contiguous(), idx_a=case["idx_a"].to(DEV))
-        dev["rd"] = NavReplay(dev["rows"].data_ptr(), R.RING)
-        o = TB._actor_rows_bc(nets, dev, B, bd, 1.0, 0.5 * 2.0 ** (K or 0))
-        q = dict(batch=o["batch"].cpu(), masks=[o["ma"].cpu(), o["mc"].cpu()], a_q=o["q"].cpu(),
-                 a_da=o["da"].cpu(), part=o["part"].cpu())
-        q.update({f"a_{n}": t for n, t in R.flat_grad_tensors(o["g"].cpu(), 2, 2, hidden,
-                                                              nets["actor"].hp, nh).items()})
-        runs[K] = q
+        nets, dev = LN.device_epoch(BR.bc_case(hidden, nh, B, bd, K=K))
+        o = LN.actor_rows(nets, dev, B, form="bc", fill=NAN, b_demo=bd, q_weight=1.0,
+                          bc_weight=0.5 * 2.0 ** (K or 0))
+        g, = LN.flat_grads([nets["actor"]], o, fill=NAN)
+        torch.cuda.synchronize()
+        runs[K] = dict(_actor_quantities(o, g, hidden, nets["actor"].hp, nh), part=o["part"].cpu())
     for K in R.SCALE_KS:
         exp = dict(actor_shifts(nh, K), part=0)
         _assert_epoch(runs[K], runs[None], exp, K, f"actor_rows_bc K {K}")
 
 
 def _pop_run(Ks):
-    """Two members (test_gpu_population_learner's, hidden 64 x 2, B = 100) through
+    """Two members (pop_support.make_td3's, hidden 64 x 2, B = 100) through
     nav_td3_actor_rows_pop and nav_td3_critic_rows_pop, each followed by its group's
     nav_mlp_wgrad_pop and nav_grad_reduce_adam_pop (for the reduced gradients; the actor phase
     first, so that neither row launch reads a network Adam has stepped). Ks[m]: member m's joint
     shift, or None. Returns per member the outputs by name."""
-    import test_gpu_population_learner as PL
     from nav._lib import lib, ptr, stream_handle
     from nav.population import PopulationLearner
     hidden, nh, B, P = 64, 2, 100, 2
-    rings = [PL.make_ring(m) for m in range(P)]
-    td3 = [PL.make_td3(m, hidden, nh, B, 1) for m in range(P)]
+    rings = [T.make_ring(m) for m in range(P)]
+    td3 = [T.make_td3(m, hidden, nh, B, 1) for m in range(P)]
     for t, ring, K in zip(td3, rings, Ks):
         if K is None:
             continue
@@ -345,7 +310,7 @@ def _actor_pair(hidden, nh, seed):
     layers = [(torch.tensor(Wl), torch.tensor(b)) for Wl, b in p]
     moved, cums = R.shift_layers(layers, 0, R.joint_shifts(nh, 0)[0])
     assert cums[-1] == 0 and any(c != 0 for c in cums)
-    return W._device_net(layers, 2, 2, hidden, nh), W._device_net(moved, 2, 2, hidden, nh)
+    return LN.device_net(layers, 2, 2, hidden, nh), LN.device_net(moved, 2, 2, hidden, nh)
 
 
 @pytest.mark.parametrize("n", [1, 97])
@@ -359,7 +324,7 @@ def test_act_ignores_the_layers_scale(nav, hidden, nh, n):
     got = []
     for net in _actor_pair(hidden, nh, 123):
         act = torch.full((n, 2), float("nan"), dtype=torch.float64, device=DEV)
-        res = W._nan(n, 2)
+        res = LN.nan(n, 2)
         assert lib().nav_act(C.byref(params_struct()), C.byref(net.desc()), n, ptr(st), ptr(gl),
                              None, None, 0, 1, ptr(act), ptr(res), stream_handle()) == 0
         torch.cuda.synchronize()
@@ -372,7 +337,6 @@ def test_act_ignores_the_layers_scale(nav, hidden, nh, n):
 def test_act_tick_ignores_the_layers_scale(nav, hidden, nh):
     """nav_act_tick, three training ticks of 97 envs (64-row blocks at any n): actions, rewards,
     replay rows, env state and flags bit-identical for both actors."""
-    import test_gpu_test_rollout as T
     from nav.vec_env import ReplayRing
     speed, angle = T.random_field(5)
     got = []
@@ -389,7 +353,7 @@ def test_act_tick_ignores_the_layers_scale(nav, hidden, nh):
         got.append(ticks + [ring.rows.clone(), env.state.clone(), env.flags.clone()])
     assert bool((got[0][0] != 0).any()) and bool((got[0][-3] != 0).any())
     for i, (u, v) in enumerate(zip(got[1], got[0])):
-        assert W._equal_nan(u, v) if u.is_floating_point() else torch.equal(u, v), i
+        assert equal_nan(u, v) if u.is_floating_point() else torch.equal(u, v), i
 
 
 @pytest.mark.parametrize("hidden,nh", ACTING_SHAPES, ids=_ids(ACTING_SHAPES))
@@ -397,7 +361,6 @@ def test_test_rollout_ignores_the_layers_scale(nav, hidden, nh):
     """nav_test_rollout, 97 envs over the full test episode length: the trajectory and every
     output bit-identical for both actors. A whole greedy episode must not notice how the actor's
     scale is distributed over its layers."""
-    import test_gpu_test_rollout as T
     from nav import config as K
     speed, angle = T.random_field(5)
     env = T.make_env(97, speed, angle)

@@ -8,39 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+from pop_support import DEV, make_learner, replay_rows, ring_of
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-
-
-def replay_rows(n, seed):
-    """Replay rows shaped like the tick's (robot.py:79-96): s in the world, clipped actions,
-    goal + demo-shaped rewards, s' = a step away, ~2 % dones."""
-    rng = np.random.default_rng(seed)
-    s = rng.uniform(0, 98.9999, (n, 2))
-    a = rng.uniform(-5, 5, (n, 2))
-    s2 = np.clip(s + 0.8 * a, 0, 98.9999)
-    goal = rng.uniform(5, 95, (n, 2))
-    r = -np.linalg.norm(s2 - goal, axis=1) - 10 * rng.uniform(0, 5, n)
-    d = (rng.uniform(size=n) < 0.02).astype(np.float64)
-    return np.concatenate([s, a, r[:, None], s2, d[:, None]], 1).astype(np.float32)
-
-
-def make_learner(B, hidden, nh, params):
-    from nav import config as K
-    from nav.mlp import DeviceMLP
-    from nav.td3 import TD3
-    pa, p1, p2 = params
-    mk = lambda di, do, p: DeviceMLP(di, do, hidden, nh, DEV).load(p)  # noqa: E731
-    cfg = K.TD3Config(batch_size=B, num_epochs=2, net=K.NetConfig(hidden=hidden, n_hidden=nh))
-    return TD3(cfg, DEV, actor=mk(2, 2, pa), critic1=mk(4, 1, p1), critic2=mk(4, 1, p2))
-
-
-def ring_of(rows):
-    from nav.vec_env import ReplayRing
-    rep = ReplayRing(len(rows), DEV)
-    rep.rows.copy_(torch.tensor(rows))
-    rep.size = len(rows)
-    return rep
 
 
 @pytest.mark.parametrize("hidden,nh,B,epochs", [(256, 2, 8192, 4), (200, 3, 1000, 4)])

@@ -2,104 +2,16 @@
 (robot-learning.py:78, 104-117) of every env in one launch, against the two-launch composition it
 fuses (bit for bit), against its own trajectory, against the CPU oracle step by step and over
 whole episodes, its start draw, and its promise to leave the trainer untouched."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
+from gpu_support import nav  # noqa: F401
+from pop_support import (DEV, clone_out, equal_tree as _equal_tree, make_actor, make_env,
+                         norm2_rows, random_field, random_starts, unfused_episode)
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 T_BITS = 12  # steps of the bitwise cases
-
-
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    import nav as navpkg
-    return navpkg
-
-
-def norm2_rows(orc, d):
-    """orc.norm2 (sqrt(fma(y, y, x * x)), the device's norm2) of every row of d [k][2]."""
-    return np.array([orc.norm2(x, y) for x, y in d.tolist()], np.float64).reshape(len(d))
-
-
-def random_field(seed):
-    rng = np.random.default_rng(seed)
-    speed = rng.uniform(0.05, 0.95, (100, 100)).astype(np.float32)  # in (0, 1)
-    angle = rng.uniform(0.0, 1.0, (100, 100)).astype(np.float32)    # in [0, 1]
-    return speed, angle
-
-
-def make_actor(hidden, nh, seed):
-    from nav.mlp import DeviceMLP
-    from oracle.td3_oracle import make_mlp_params
-    p = make_mlp_params(seed, [2] + [hidden] * nh + [2])
-    return DeviceMLP(2, 2, hidden, nh, DEV).load(p), [(torch.tensor(W), torch.tensor(b))
-                                                      for W, b in p]
-
-
-def make_env(n, speed, angle, **overrides):
-    from nav.vec_env import VecEnv, make_field
-    return VecEnv(n, make_field(speed, angle, DEV), seed=77, demo_flag=False, device=DEV,
-                  **overrides)
-
-
-def random_starts(env, seed):
-    """Uniform starts in the world; every 5th env one unit from its goal, so that some rows stop
-    at the first step while their tile goes on."""
-    g = torch.Generator().manual_seed(seed)
-    st = torch.rand(env.n, 2, generator=g, dtype=torch.float64) * 98.0
-    near = torch.arange(env.n) % 5 == 0
-    st[near] = env.goal.cpu()[near] + torch.tensor([0.6, -0.8], dtype=torch.float64)
-    return st.clamp_(0.0, 98.0).to(DEV)
-
-
-def clone_out(out):
-    return {k: v.clone() for k, v in out.items()}
-
-
-def unfused_episode(orc, env, actor, start, T):
-    """The composition the kernel fuses: per step nav_act(mode=1) then nav_env_step on a scratch
-    VecEnv, stopped rows masked back, the stop test on the CPU with the oracle's norm2."""
-    from nav._lib import lib, ptr, stream_handle
-    from nav.vec_env import VecEnv
-    n = env.n
-    sc = VecEnv(n, env.field, device=DEV, init=False)
-    sc.goal.copy_(env.goal)
-    sc.state.copy_(start)
-    thr = env.p.goal_threshold
-    goal = env.goal.cpu().numpy()
-    action = torch.zeros(n, 2, dtype=torch.float64, device=DEV)
-    d = actor.desc()
-    run = np.ones(n, bool)
-    reached = np.zeros(n, np.uint8)
-    steps = np.full(n, T, np.int32)
-    best = np.full(n, np.inf)
-    traj = torch.zeros(T, n, 2, dtype=torch.float64, device=DEV)
-    for t in range(1, T + 1):
-        prev = sc.state.clone()
-        lib().nav_act(C.byref(sc.p), C.byref(d), n, ptr(sc.state), ptr(sc.goal), None, None, 0, 1,
-                      ptr(action), None, stream_handle())
-        sc.step(action)
-        keep = torch.from_numpy(~run).to(DEV)
-        sc.state.copy_(torch.where(keep[:, None], prev, sc.state))
-        traj[t - 1] = sc.state
-        s = sc.state.cpu().numpy()
-        idx = np.nonzero(run)[0]
-        dist = norm2_rows(orc, s[idx] - goal[idx])
-        best[idx] = np.minimum(best[idx], dist)
-        hit = idx[dist <= thr]
-        reached[hit] = 1
-        steps[hit] = t
-        run[hit] = False
-    return {"traj": traj, "final_state": sc.state.clone(), "reached": torch.from_numpy(reached),
-            "steps": torch.from_numpy(steps), "best_distance": torch.from_numpy(best)}
-
-
 _cases = {}
 
 
@@ -285,7 +197,7 @@ def _reference_closed_loop(g, cap):
     (asserted here); for one that did, the reference exits before its `<` update
     (robot-learning.py:110-114) and never reports the variable, so the minimum includes the
     reaching step's recorded distance, as nav_test_rollout documents."""
-    from test_oracle_branches_cpu import episode_slices
+    from trace_support import episode_slices
     steps, reached, final, best = [], [], [], []
     for e, ix in enumerate(episode_slices(g, "b_")):
         k = min(len(ix), cap)
@@ -381,21 +293,6 @@ def test_start_draw(nav, orc):
         firsts[episode] = (s0, drawn["traj"][0].cpu().numpy())
     assert np.all(np.any(firsts[0][0] != firsts[3][0], axis=1))
     assert np.any(firsts[0][1] != firsts[3][1])
-
-
-def _equal_tree(a, b, path=""):
-    if isinstance(a, dict):
-        assert a.keys() == b.keys(), path
-        for k in a:
-            _equal_tree(a[k], b[k], f"{path}/{k}")
-    elif isinstance(a, (list, tuple)):
-        assert len(a) == len(b), path
-        for i, (x, y) in enumerate(zip(a, b)):
-            _equal_tree(x, y, f"{path}/{i}")
-    elif torch.is_tensor(a):
-        assert torch.equal(a, b), path
-    else:
-        assert a == b, path
 
 
 def test_evaluate_leaves_training_untouched(nav):

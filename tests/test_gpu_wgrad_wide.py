@@ -9,18 +9,11 @@ Per slab the scale is that slab's own max |dW|, which is no larger than the sum'
 import pytest
 import torch
 
+from gpu_support import nav  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 D_IN, D_OUT, NH = 4, 1, 2
-
-
-@pytest.fixture(scope="module")
-def nav():
-    from nav import _lib
-    _lib.require_gpu()
-    _lib.lib()
-    import nav as navpkg
-    return navpkg
 
 
 def make_net(hidden, seed):

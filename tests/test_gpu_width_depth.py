@@ -20,17 +20,21 @@ import numpy as np
 import pytest
 import torch
 
+import launches as LN
 import mlp_ref as R
+import pop_support as T
+from gpu_support import equal_nan, ids as _ids
+from launches import nan as _nan
 
 pytestmark = pytest.mark.gpu
 DEV = R.DEV
 LOG = R.ParityLog()
 BIG = 16421  # 64-row blocks (RT = 2), the last one partial
-SEED = 1707366464
+NAN = float("nan")
 
 
 @pytest.fixture(scope="module")
-def nav():
+def nav():  # this module's own: the teardown writes the parity log
     from nav import _lib
     _lib.require_gpu()
     _lib.lib()
@@ -39,10 +43,6 @@ def nav():
     path = os.environ.get("NAV_WIDTH_DEPTH_PARITY")
     if path:
         LOG.write(path)
-
-
-def _ids(cases):
-    return ["-".join(str(v) for v in c) for c in cases]
 
 
 # ---- (a) the unfused chain ----
@@ -64,52 +64,9 @@ def test_unfused_chain_vs_fp64(nav, hidden, nh, kind, M):
 
 
 # ---- (b), (c), (d): the fused TD3 epoch ----
-def _device_net(layers, d_in, d_out, hidden, nh):
-    from nav.mlp import DeviceMLP
-    return DeviceMLP(d_in, d_out, hidden, nh, DEV).load([(W.numpy(), b.numpy()) for W, b in layers])
-
-
-def _nan(*shape):
-    return torch.full(shape, float("nan"), device=DEV)
-
-
 def _epoch_setup(hidden, nh, B):
-    from nav._lib import NavReplay
     case = R.epoch_case(hidden, nh, B)
-    nets = {}
-    for name, layers in case["layers"].items():
-        d_in, d_out = (2, 2) if name in ("ta", "actor", "atgt") else (4, 1)
-        nets[name] = _device_net(layers, d_in, d_out, hidden, nh)
-    dev = dict(rows=case["rows"].to(DEV).contiguous(), idx=case["idx"].to(DEV),
-               idx_a=case["idx_a"].to(DEV), eps=case["eps"].to(DEV).contiguous())
-    dev["rd"] = NavReplay(dev["rows"].data_ptr(), R.RING)
-    return case, nets, dev
-
-
-def _critic_rows(nets, dev, B, split):
-    """nav_td3_critic_rows with each online critic's row backward and the middle layers saved,
-    into NaN-prefilled buffers."""
-    from nav._lib import descs, lib, parr, ptr, stream_handle
-    L = lib()
-    cr = [nets["cr0"], nets["cr1"]]
-    hp, nh = cr[0].hp, cr[0].n_hidden
-    mid = cr[0].middle_layers()
-    nblk = L.nav_mlp_row_blocks(B)
-    ec = L.nav_mlp_edge_count(4, 1, hp, nh)
-    o = dict(batch=_nan(B, 8), dq=[_nan(B), _nan(B)], lp=_nan(2, nblk),
-             es=[_nan(nblk, ec), _nan(nblk, ec)], acts=[_nan(nh, B, hp), _nan(nh, B, hp)],
-             dz=[_nan(nh, B, hp), _nan(nh, B, hp)], masks=[c.mask_buffer(B) for c in cr])
-    assert L.nav_td3_critic_rows(
-        C.byref(nets["ta"].desc()), descs(nets["tc0"], nets["tc1"]), descs(*cr),
-        C.byref(dev["rd"]), R.RING, B, ptr(dev["idx"]), SEED & 0xFFFFFFFF, SEED >> 32, 3,
-        ptr(dev["eps"]), 0.2, 0.5, 5.0, 0.99, ptr(o["batch"]), parr(*o["dq"]),
-        parr(o["lp"][0], o["lp"][1]), parr(*o["es"]), parr(*o["acts"]), mid, parr(*o["masks"]), 1,
-        parr(*o["dz"]), mid, split, stream_handle()) == 0
-    return o
-
-
-def _equal_nan(a, b):
-    return torch.equal(a.isnan(), b.isnan()) and torch.equal(a.nan_to_num(), b.nan_to_num())
+    return (case, *LN.device_epoch(case))
 
 
 EPOCH_CASES = [(h, nh, B) for h, nh in R.SHAPES for B in (33, 100)] + [(24, 2, BIG), (150, 2, BIG)]
@@ -122,31 +79,21 @@ def test_fused_critic_epoch_vs_fp64(nav, hidden, nh, B):
     in fp64 from the f32 weights and rows: batch == rows[idx], dq against 2 (q - y) / B, sum
     (loss_part) / B against the loss, both critics' flat gradients tensor by tensor; split_twins
     0 and 1 bit-identical."""
-    from nav._lib import descs, lib, parr, ptr, stream_handle
-    L = lib()
-    s = stream_handle()
+    from nav._lib import lib
     case, nets, dev = _epoch_setup(hidden, nh, B)
     cr = [nets["cr0"], nets["cr1"]]
     hp = cr[0].hp
-    o, o1 = _critic_rows(nets, dev, B, 0), _critic_rows(nets, dev, B, 1)
-    nblk = o["lp"].shape[1]
+    o, o1 = (LN.critic_rows(nets, dev, B, fill=NAN, split=split) for split in (0, 1))
     grads = {}
-    for splits in sorted({int(L.nav_mlp_wgrad_splits(2, 1, hp, nh, B)), 3}):
-        hs = [_nan(splits, max(4, L.nav_mlp_hidden_count(hp, nh))) for _ in range(2)]
-        assert L.nav_mlp_wgrad(descs(*cr), 2, B, ptr(o["batch"]), 8, 0, parr(*o["acts"]),
-                               parr(*o["dz"]), parr(*o["dq"]), 1, parr(*o["masks"]), parr(*hs),
-                               splits, s) == 0
-        for k in range(2):
-            g = _nan(cr[k].count)
-            assert L.nav_grad_reduce(C.byref(cr[k].desc()), ptr(hs[k]), splits, ptr(o["es"][k]),
-                                     nblk, ptr(g), s) == 0
+    for splits in sorted({int(lib().nav_mlp_wgrad_splits(2, 1, hp, nh, B)), 3}):
+        for k, g in enumerate(LN.flat_grads(cr, o, splits=splits, fill=NAN)):
             grads[splits, k] = g
     torch.cuda.synchronize()
     for key in ("batch", "lp"):
         assert torch.equal(o[key], o1[key]), key
     for key in ("dq", "es", "masks", "acts", "dz"):  # unsaved layers stay NaN in both
         for k in range(2):
-            assert _equal_nan(o[key][k].float(), o1[key][k].float()), (key, k)
+            assert equal_nan(o[key][k].float(), o1[key][k].float()), (key, k)
     batch = case["rows"][case["idx"]]
     assert torch.equal(o["batch"].cpu(), batch)
     bits = [R.relu_bits(o["masks"][k], nh, hp, hidden, B) for k in range(2)]
@@ -164,29 +111,10 @@ def test_fused_critic_epoch_vs_fp64(nav, hidden, nh, B):
 
 
 def _actor_rows(nets, dev, B):
-    """nav_td3_actor_rows -> nav_mlp_wgrad -> nav_grad_reduce as TD3.train_actor issues them,
-    NaN-prefilled buffers; the reduce's inputs are kept for the update step."""
-    from nav._lib import descs, lib, parr, ptr, stream_handle
-    L = lib()
-    s = stream_handle()
-    actor, critic = nets["actor"], nets["cr0"]
-    hp, nh = actor.hp, actor.n_hidden
-    mid = actor.middle_layers()
-    nblk = L.nav_mlp_row_blocks(B)
-    o = dict(batch=_nan(B, 8), q=_nan(B), da=_nan(B, 2), acts=_nan(nh, B, hp), dz=_nan(nh, B, hp),
-             ma=actor.mask_buffer(B), mc=critic.mask_buffer(B),
-             es=_nan(nblk, L.nav_mlp_edge_count(2, 2, hp, nh)), nblk=nblk)
-    assert L.nav_td3_actor_rows(
-        C.byref(actor.desc()), C.byref(critic.desc()), C.byref(dev["rd"]), R.RING, B,
-        ptr(dev["idx_a"]), SEED & 0xFFFFFFFF, SEED >> 32, 3, ptr(o["batch"]), ptr(o["q"]),
-        ptr(o["da"]), ptr(o["acts"]), mid, ptr(o["dz"]), mid, ptr(o["ma"]), ptr(o["mc"]),
-        ptr(o["es"]), s) == 0
-    o["splits"] = int(L.nav_mlp_wgrad_splits(1, 2, hp, nh, B))
-    o["hs"] = _nan(o["splits"], max(4, L.nav_mlp_hidden_count(hp, nh)))
-    assert L.nav_mlp_wgrad(descs(actor), 1, B, ptr(o["batch"]), 8, 0, parr(o["acts"]),
-                           parr(o["dz"]), parr(o["da"]), 2, parr(o["ma"]), parr(o["hs"]),
-                           o["splits"], s) == 0
-    return o
+    """nav_td3_actor_rows -> nav_mlp_wgrad as TD3.train_actor issues them, NaN-prefilled buffers;
+    the reduce's inputs are kept for the update step."""
+    o = LN.actor_rows(nets, dev, B, form="plain", fill=NAN)
+    return LN.wgrad([nets["actor"]], o, fill=NAN)
 
 
 @pytest.mark.parametrize("hidden,nh,B", EPOCH_CASES, ids=_ids(EPOCH_CASES))
@@ -196,15 +124,11 @@ def test_fused_actor_epoch_vs_fp64(nav, hidden, nh, B):
     injected: q, da and the actor's flat gradient tensor by tensor.
     The critic's layer-0 input holds pi(s), itself a computed quantity within its bar of the
     reference's, so that layer's kink band is widened by |W0[:, 2:4]| @ (bar_a * max |a|)."""
-    from nav._lib import lib, ptr, stream_handle
-    L = lib()
     case, nets, dev = _epoch_setup(hidden, nh, B)
     actor = nets["actor"]
     hp = actor.hp
-    o = _actor_rows(nets, dev, B)
-    g = _nan(actor.count)
-    assert L.nav_grad_reduce(C.byref(actor.desc()), ptr(o["hs"]), o["splits"], ptr(o["es"]),
-                             o["nblk"], ptr(g), stream_handle()) == 0
+    o = LN.actor_rows(nets, dev, B, form="plain", fill=NAN)
+    g, = LN.flat_grads([actor], o, fill=NAN)
     torch.cuda.synchronize()
     rows_a = case["rows"][case["idx_a"]]
     assert torch.equal(o["batch"].cpu(), rows_a)
@@ -257,7 +181,7 @@ def test_update_step_vs_fp64(nav, hidden, nh):
     c0 = [t.params.cpu().double() for t in ctgt]
     b1, b2, eps, ss, bc2s, tau = (R.f32c(x) for x in (0.9, 0.999, 1e-8, 1e-3, 0.5, 0.25))
     assert L.nav_grad_reduce_adam_polyak(
-        descs(actor), 1, parr(o["hs"]), o["splits"], parr(o["es"]), o["nblk"], parr(g), parr(m),
+        descs(actor), 1, parr(*o["hs"]), o["splits"], parr(o["es"]), o["nblk"], parr(g), parr(m),
         parr(v), b1, b2, eps, (C.c_float * 1)(ss), (C.c_float * 1)(bc2s), descs(atgt),
         descs(*ctgt), descs(*crit), 2, tau, stream_handle()) == 0
     torch.cuda.synchronize()
@@ -350,7 +274,7 @@ def test_act_tick_is_bit_identical(nav, hidden, nh):
     assert torch.equal(a.env.flags, b.env.flags)
     for t, (x, y) in enumerate(zip(ga, gb)):
         for i, (u, v) in enumerate(zip(x, y)):
-            assert _equal_nan(u, v), (t, i)
+            assert equal_nan(u, v), (t, i)
     for k, net in a.td3.networks().items():
         assert torch.equal(net.params, b.td3.networks()[k].params), k
 
@@ -359,7 +283,6 @@ def test_act_tick_is_bit_identical(nav, hidden, nh):
 def test_test_rollout_is_bit_identical(nav, orc, hidden, nh):
     """nav_test_rollout over 97 envs and 8 steps against the host loop of nav_act(mode 1) ->
     nav_env_step it fuses (tests/test_gpu_test_rollout.py), bit for bit."""
-    import test_gpu_test_rollout as T
     speed, angle = T.random_field(5)
     env = T.make_env(97, speed, angle)
     actor, _ = T.make_actor(hidden, nh, 31)

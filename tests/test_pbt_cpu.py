@@ -3,12 +3,17 @@ nav_td3_pop_state_build and nav_td3_pop_exploit (every rejected condition return
 any HIP call and without following a pointer: no kernel is launched by these calls, so no GPU is
 needed), the state table's size, and the pure selection and explore rules."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from abi_args import member_field as _member_field
+from abi_args import net_field as _net_field
+from abi_args import set_attr as _set
+from abi_args import td3_member
 from conftest import PKG
 
 LIB = os.path.join(PKG, "nav", "libnavenv.so")
@@ -25,20 +30,7 @@ def navlib():
     return _lib.lib()
 
 
-def member(hidden=H, n_hidden=NH, cap=CAP):
-    """A nav_td3_member with its learner state on fake pointers and everything else null."""
-    from nav._lib import NavMlp, NavReplay, NavTd3Member
-    m = NavTd3Member()
-    net = lambda di, do: NavMlp(di, do, hidden, (hidden + 31) // 32 * 32, n_hidden,  # noqa: E731
-                                FAKE, FAKE)
-    m.actor, m.target_actor = net(2, 2), net(2, 2)
-    for i in range(2):
-        m.critics[i], m.target_critics[i] = net(4, 1), net(4, 1)
-    m.replay = NavReplay(FAKE, cap)
-    m.m_actor = m.v_actor = FAKE
-    for i in range(2):
-        m.m_critic[i] = m.v_critic[i] = FAKE
-    return m
+member = functools.partial(td3_member, hidden=H, n_hidden=NH, cap=CAP, state_only=True)
 
 
 class Args:
@@ -61,31 +53,9 @@ class Args:
                                                              self.rows, None)}
 
 
-def _set(attr, value):
-    def f(a):
-        setattr(a, attr, value)
-    return f
-
-
 def _pairs(src, dst):
     def f(a):
         a.src, a.dst = src, dst
-    return f
-
-
-def _member_field(name, value, index=None, m=1):
-    def f(a):
-        if index is None:
-            setattr(a.m[m], name, value)
-        else:
-            getattr(a.m[m], name)[index] = value
-    return f
-
-
-def _net_field(net, field, value, index=None, m=1):
-    def f(a):
-        d = getattr(a.m[m], net)
-        setattr(d if index is None else d[index], field, value)
     return f
 
 

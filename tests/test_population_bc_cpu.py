@@ -5,11 +5,16 @@ is needed; an accepted call would launch, so every case here has to be refused),
 size, the group-to-member bookkeeping of the members' demonstration tails, and what `explore` may
 perturb."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
 import pytest
 
+from abi_args import member_field as _member_field
+from abi_args import net_field as _net_field
+from abi_args import set_attr as _set
+from abi_args import td3_member
 from conftest import PKG
 
 LIB = os.path.join(PKG, "nav", "libnavenv.so")
@@ -28,26 +33,7 @@ def navlib():
     return _lib.lib()
 
 
-def member(hidden=H, n_hidden=NH, cap=CAP):
-    """A valid nav_td3_member on fake pointers (tests/test_population_learner_cpu.py's), its
-    index arrays set as the BC entry points want them."""
-    from nav._lib import NavMlp, NavReplay, NavTd3Member
-    m = NavTd3Member()
-    net = lambda di, do: NavMlp(di, do, hidden, (hidden + 31) // 32 * 32, n_hidden,  # noqa: E731
-                                FAKE, FAKE)
-    m.actor, m.target_actor = net(2, 2), net(2, 2)
-    for i in range(2):
-        m.critics[i], m.target_critics[i] = net(4, 1), net(4, 1)
-    m.replay = NavReplay(FAKE, cap)
-    m.actor_lr, m.critic_lr = 1e-4, 1e-3
-    m.policy_noise, m.noise_clip, m.max_action, m.gamma, m.tau = 0.2, 0.5, 5.0, 0.99, 0.005
-    for name, kind in m._fields_:
-        if kind is C.c_void_p and name not in ("idx_critic", "idx_actor", "eps"):
-            setattr(m, name, FAKE)
-        elif kind is C.c_void_p * 2:
-            getattr(m, name)[0] = getattr(m, name)[1] = FAKE
-    m.idx_critic, m.idx_actor = IDX_C, IDX_A
-    return m
+member = functools.partial(td3_member, hidden=H, n_hidden=NH, cap=CAP, idx=(IDX_C, IDX_A))
 
 
 def member_bc(b_demo=7, n_demo=37, q=1.0, bc=0.5):
@@ -80,28 +66,6 @@ class Args:
 
 ALL = ("build", "mix", "actor")
 LAUNCH = ("mix", "actor")
-
-
-def _set(attr, value):
-    def f(a):
-        setattr(a, attr, value)
-    return f
-
-
-def _member_field(name, value, index=None, m=1):
-    def f(a):
-        if index is None:
-            setattr(a.m[m], name, value)
-        else:
-            getattr(a.m[m], name)[index] = value
-    return f
-
-
-def _net_field(net, field, value, index=None, m=1):
-    def f(a):
-        d = getattr(a.m[m], net)
-        setattr(d if index is None else d[index], field, value)
-    return f
 
 
 def _bc_field(name, value, m=1):

@@ -2,12 +2,16 @@
 *_pop launch entry points (every rejected condition returns NAV_EINVAL before any HIP call: no
 kernel is launched by these calls, so no GPU is needed), nav_mlp_wgrad_splits_pop against
 nav_mlp_wgrad_splits, and the trainer's keyword check."""
-import ctypes as C
+import functools
 import os
 import subprocess
 
 import pytest
 
+from abi_args import member_field as _member_field
+from abi_args import net_field as _net_field
+from abi_args import set_attr as _set
+from abi_args import td3_member
 from conftest import PKG
 
 LIB = os.path.join(PKG, "nav", "libnavenv.so")
@@ -23,24 +27,7 @@ def navlib():
     return _lib.lib()
 
 
-def member(hidden=H, n_hidden=NH, cap=CAP):
-    """A valid nav_td3_member on fake pointers."""
-    from nav._lib import NavMlp, NavReplay, NavTd3Member
-    m = NavTd3Member()
-    net = lambda di, do: NavMlp(di, do, hidden, (hidden + 31) // 32 * 32, n_hidden,  # noqa: E731
-                                FAKE, FAKE)
-    m.actor, m.target_actor = net(2, 2), net(2, 2)
-    for i in range(2):
-        m.critics[i], m.target_critics[i] = net(4, 1), net(4, 1)
-    m.replay = NavReplay(FAKE, cap)
-    m.actor_lr, m.critic_lr = 1e-4, 1e-3
-    m.policy_noise, m.noise_clip, m.max_action, m.gamma, m.tau = 0.2, 0.5, 5.0, 0.99, 0.005
-    for name, kind in m._fields_:
-        if kind is C.c_void_p and name not in ("idx_critic", "idx_actor", "eps"):
-            setattr(m, name, FAKE)
-        elif kind is C.c_void_p * 2:
-            getattr(m, name)[0] = getattr(m, name)[1] = FAKE
-    return m
+member = functools.partial(td3_member, hidden=H, n_hidden=NH, cap=CAP)
 
 
 class Args:
@@ -76,28 +63,6 @@ class Args:
 
 ALL = ("build", "critic", "actor", "wgrad", "reduce")
 ROWS = ("build", "critic", "actor")
-
-
-def _set(attr, value):
-    def f(a):
-        setattr(a, attr, value)
-    return f
-
-
-def _member_field(name, value, index=None, m=1):
-    def f(a):
-        if index is None:
-            setattr(a.m[m], name, value)
-        else:
-            getattr(a.m[m], name)[index] = value
-    return f
-
-
-def _net_field(net, field, value, index=None, m=1):
-    def f(a):
-        d = getattr(a.m[m], net)
-        setattr(d if index is None else d[index], field, value)
-    return f
 
 
 def _capacity(a):
